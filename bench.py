@@ -24,13 +24,21 @@ the hot path over one batch of synthetic input that is already resident in HBM.
                on the same batch, with its own roofline (rc_encode_kernel) and CPU baseline
                (oracle/_ref/libsqz_ref_rc.so).  Not BASELINE.json's metric: a secondary line.
 
-The decode pass over the produced streams is timed right after, with the same K and W, and
-reported in the same line (`decode_MBps`), together with
+A plain run sets up, warms up, times the K encode steps and prints the line (`value`, `ms_per_step`,
+`compressed_ratio`); nothing else runs.  --full adds everything else the benchmark measures or checks:
+the decode pass over the produced streams, timed right after with the same K and W and reported in the
+same line (`decode_MBps`), the round-trip check, per-kernel times (`kernels_ms`), `secondary`, the
+`with_transfer` leg (N>1, strong), and
   roofline      the dominant kernel of the encode step (longest average launch, HIP
                 events on the launch stream, measured live in this process) vs the HBM roof
   cpu_baseline  the reference itself (oracle/_ref, built in the build container and
                 shipped as a .so) or, if absent, the oracle restatement, timed
                 single-thread on a bounded sample of the same workload (rank 0, N=1)
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's blocks) as
+DIR/<name>.npy, float32 / float64: out_bytes, out_off, err and a fixed sample of the compressed
+slabs (out_sample, at the positions out_sample_pos within each block's stream).  The input is a
+function of the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import datetime
@@ -76,6 +84,31 @@ def cpu_baseline(n_sample_blocks, block_bytes, win_bits):
                       f"({n_sample_blocks} x {block_bytes} B, window 2^{win_bits}), "
                       f"encode {enc_s:.1f} s + decode {dec_s:.2f} s on one host core "
                       f"of {os.cpu_count()}"}
+
+
+DUMP_SAMPLE = 1 << 22       # sampled compressed bytes per dump: 16 MB of float32 + 32 MB of float64 positions
+
+
+def dump_outputs(path, out, out_off, out_bytes, err):
+    """--dump-outputs: the encode step's (out, out_off, out_bytes, err) as .npy.  The slabs (about 1 GB on
+    the default batch, the bytes past each stream unwritten) are sampled: per block the same fixed
+    fractions of its stream length (seed 0, the first byte always), so equal streams give equal files."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = out_bytes.numel()
+    sizes = out_bytes.cpu().numpy()
+    frac = np.sort(np.random.default_rng(0).random(max(1, min(1024, DUMP_SAMPLE // n))))
+    frac[0] = 0.0
+    pos = np.floor(frac[None, :] * sizes[:, None]).astype(np.int64)            # (n, per block), < sizes[b]
+    idx = torch.from_numpy(out_off[:-1].cpu().numpy()[:, None] + pos).to(out.device)
+    arrays = {"out_sample": out[idx].to(torch.float32).cpu().numpy(),
+              "out_sample_pos": pos.astype(np.float64),
+              "out_bytes": sizes.astype(np.float64),
+              "out_off": out_off.cpu().numpy().astype(np.float64),
+              "err": err.cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def kernel_build_id():
@@ -194,7 +227,7 @@ def run_rc(args, torch, dist, batch, shard, info, dev, comm_dev, rank, world, lo
     for _ in range(args.warmup):
         enc_step()
     barrier()
-    batch.set_timing(True)
+    batch.set_timing(args.full)                  # per-kernel HIP events: --full only
     batch.get_timing(reset=True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -202,36 +235,37 @@ def run_rc(args, torch, dist, batch, shard, info, dev, comm_dev, rank, world, lo
     barrier()
     enc_s = time.perf_counter() - t0
     tim = batch.get_timing(reset=True)
-    assert int(err.abs().sum()) == 0, "rc encode reported errors"
-    for _ in range(args.warmup):
-        dec_step()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        dec_step()
-    barrier()
-    dec_s = time.perf_counter() - t0
-    dtim = batch.get_timing(reset=True)
     batch.set_timing(False)
-    assert int(derr.abs().sum()) == 0, "rc decode reported errors"
-    if not args.no_verify:
-        assert torch.equal(back, d_in), "rc round trip differs"
-        assert torch.equal(cons, ob), "rc decoder did not consume exactly the stream"
+    assert int(err.abs().sum()) == 0, "rc encode reported errors"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, out_off, ob, err)
+    if args.full:
+        for _ in range(args.warmup):
+            dec_step()
+        barrier()
+        batch.set_timing(True)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            dec_step()
+        barrier()
+        dec_s = time.perf_counter() - t0
+        dtim = batch.get_timing(reset=True)
+        batch.set_timing(False)
+        assert int(derr.abs().sum()) == 0, "rc decode reported errors"
+        if not args.no_verify:
+            assert torch.equal(back, d_in), "rc round trip differs"
+            assert torch.equal(cons, ob), "rc decoder did not consume exactly the stream"
     comp_bytes = int(ob.sum().item())
     if world > 1:
         enc_s = shard.max_over_ranks(enc_s, comm_dev)
-        dec_s = shard.max_over_ranks(dec_s, comm_dev)
+        if args.full:
+            dec_s = shard.max_over_ranks(dec_s, comm_dev)
         comp_total = shard.sum_over_ranks(float(comp_bytes), comm_dev)
     else:
         comp_total = float(comp_bytes)
     if rank != 0:
         return
     in_total = float(total_blocks) * bb
-    enc_ms = tim["rc_encode_kernel"][0] / max(tim["rc_encode_kernel"][1], 1)
-    dec_ms = dtim["rc_decode_kernel"][0] / max(dtim["rc_decode_kernel"][1], 1)
-    algo = n * bb + comp_bytes                   # every input byte read once, every output byte written once
-    achieved = algo / (enc_ms * 1e-3) / 1e9
-    rc_traffic, rc_traffic_note = measured_traffic("rc_encode_kernel")   # (tools/r03_final.sh PART=rc adds the R-era kernels)
     line = {
         "metric": "R-era range coder (SURVEY.md 8f-1): encode MB/s + decode MB/s, batched blocks",
         "value": round(in_total / enc_s * args.steps / 1e6, 3), "unit": "MB/s",
@@ -244,18 +278,26 @@ def run_rc(args, torch, dist, batch, shard, info, dev, comm_dev, rank, world, lo
                                "runs, src/sqz.c:590-596,717-743) -- NOT BASELINE.json's metric, a secondary line",
                    "total_blocks": total_blocks, "blocks_per_gpu": n, "block_bytes": bb, "codec": "rc",
                    "device": info["name"]},
-        "decode_MBps": round(in_total / dec_s * args.steps / 1e6, 3),
-        "decode_ms_per_step": round(dec_s / args.steps * 1e3, 3),
         "compressed_ratio": round(comp_total / in_total, 5),
-        "kernels_ms": {"rc_encode_kernel": round(enc_ms, 3), "rc_decode_kernel": round(dec_ms, 3)},
-        "roofline": {"bound": "hbm", "kernel": "rc_encode_kernel", "achieved": round(achieved, 4),
-                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 7),
-                     "traffic": rc_traffic, "traffic_note": rc_traffic_note,
-                     "algorithmic_bytes_per_launch": algo,
-                     "decode_frac_of_hbm_roof": round(algo / (dec_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 7)},
     }
-    if world == 1 and args.cpu_blocks > 0:
-        line["cpu_baseline"] = cpu_baseline_rc(args.cpu_blocks, bb)
+    if args.full:
+        enc_ms = tim["rc_encode_kernel"][0] / max(tim["rc_encode_kernel"][1], 1)
+        dec_ms = dtim["rc_decode_kernel"][0] / max(dtim["rc_decode_kernel"][1], 1)
+        algo = n * bb + comp_bytes                   # every input byte read once, every output byte written once
+        achieved = algo / (enc_ms * 1e-3) / 1e9
+        rc_traffic, rc_traffic_note = measured_traffic("rc_encode_kernel")   # (tools/r03_final.sh PART=rc adds the R-era kernels)
+        line.update({
+            "decode_MBps": round(in_total / dec_s * args.steps / 1e6, 3),
+            "decode_ms_per_step": round(dec_s / args.steps * 1e3, 3),
+            "kernels_ms": {"rc_encode_kernel": round(enc_ms, 3), "rc_decode_kernel": round(dec_ms, 3)},
+            "roofline": {"bound": "hbm", "kernel": "rc_encode_kernel", "achieved": round(achieved, 4),
+                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 7),
+                         "traffic": rc_traffic, "traffic_note": rc_traffic_note,
+                         "algorithmic_bytes_per_launch": algo,
+                         "decode_frac_of_hbm_roof": round(algo / (dec_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 7)},
+        })
+        if world == 1 and args.cpu_blocks > 0:
+            line["cpu_baseline"] = cpu_baseline_rc(args.cpu_blocks, bb)
     print(json.dumps(line), flush=True)
 
 
@@ -280,7 +322,14 @@ def main():
                          "of HEAD (SURVEY.md section 8f-1), a secondary line")
     ap.add_argument("--finder", choices=["index", "scan"], default="index",
                     help="stage-1 match finder: index (default) or the brute-force scan")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure / check everything besides the headline figure: decode pass, round trip, "
+                         "per-kernel times, roofline, secondary figures, cpu_baseline, with_transfer (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -325,8 +374,6 @@ def main():
     d_in = batch.zipf_blocks(n, bb, first_block=lo, device=dev)
     in_off = batch.uniform_offsets(n, bb, device=dev)
     enc = batch.Encoder(n, n * bb, sqz_amd.bound(bb), device=dev)
-    d_back = torch.empty_like(d_in)
-    derr = torch.zeros(n, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
 
     def barrier():
@@ -338,14 +385,11 @@ def main():
     def encode_step():
         return enc.encode(d_in, in_off, 1 << wb)
 
-    def decode_step(out, out_off):
-        batch.decode_blocks(out, out_off, n, d_back, in_off, derr)
-
     # ---- encode: W warmup + K timed steps -------------------------------------
     for _ in range(args.warmup):
         encode_step()
     barrier()
-    batch.set_timing(True)
+    batch.set_timing(args.full)                    # per-kernel HIP events: --full only
     batch.get_timing(reset=True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -355,43 +399,55 @@ def main():
     tim = batch.get_timing(reset=True)
     batch.set_timing(False)
     assert int(err.abs().sum()) == 0, "encode reported errors"
-    # ---- secondary figures: what the serial stages actually chew through.
-    # tok_count[n] is the head of the encode scratch (include/sqz/sqz.h); block 0's token
-    # words follow at the 256-byte-aligned offset.  Not timed.
-    tok_counts = enc.scratch[:4 * n].view(torch.int32)
-    tokens_rank = int(tok_counts.to(torch.int64).sum())
-    head = (4 * n + 255) // 256 * 256
-    t0c = int(tok_counts[0])
-    tw = enc.scratch[head:head + 4 * t0c].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    tlen = torch.where((tw >> 31) != 0, (tw >> 16) & 0x1FF, torch.ones_like(tw))
-    tpos = torch.cumsum(tlen, 0) - tlen                      # start position of every token
-    cand0 = int(torch.clamp(tpos, max=(1 << wb) - 1).sum())  # scan: min(i, window-1) candidates per token
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, out_off, out_bytes, err)
     comp_bytes = int(out_bytes.sum().item())
 
-    # ---- decode: same K / W ----------------------------------------------------
-    for _ in range(args.warmup):
-        decode_step(out, out_off)
-    barrier()
-    batch.set_timing(True)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        decode_step(out, out_off)
-    barrier()
-    dec_s = time.perf_counter() - t0
-    dtim = batch.get_timing(reset=True)
-    batch.set_timing(False)
-    assert int(derr.abs().sum()) == 0, "decode reported errors"
-    if not args.no_verify:
-        assert torch.equal(d_back, d_in), "round trip differs"
+    if args.full:
+        # ---- secondary figures: what the serial stages actually chew through.
+        # tok_count[n] is the head of the encode scratch (include/sqz/sqz.h); block 0's token
+        # words follow at the 256-byte-aligned offset.  Not timed.
+        tok_counts = enc.scratch[:4 * n].view(torch.int32)
+        tokens_rank = int(tok_counts.to(torch.int64).sum())
+        head = (4 * n + 255) // 256 * 256
+        t0c = int(tok_counts[0])
+        tw = enc.scratch[head:head + 4 * t0c].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        tlen = torch.where((tw >> 31) != 0, (tw >> 16) & 0x1FF, torch.ones_like(tw))
+        tpos = torch.cumsum(tlen, 0) - tlen                      # start position of every token
+        cand0 = int(torch.clamp(tpos, max=(1 << wb) - 1).sum())  # scan: min(i, window-1) candidates per token
+
+        # ---- decode: same K / W ----------------------------------------------------
+        d_back = torch.empty_like(d_in)
+        derr = torch.zeros(n, dtype=torch.int32, device=dev)
+
+        def decode_step(out, out_off):
+            batch.decode_blocks(out, out_off, n, d_back, in_off, derr)
+
+        for _ in range(args.warmup):
+            decode_step(out, out_off)
+        barrier()
+        batch.set_timing(True)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            decode_step(out, out_off)
+        barrier()
+        dec_s = time.perf_counter() - t0
+        dtim = batch.get_timing(reset=True)
+        batch.set_timing(False)
+        assert int(derr.abs().sum()) == 0, "decode reported errors"
+        if not args.no_verify:
+            assert torch.equal(d_back, d_in), "round trip differs"
 
     if world > 1:
         enc_s = shard.max_over_ranks(enc_s, comm_dev)
-        dec_s = shard.max_over_ranks(dec_s, comm_dev)
         comp_total = shard.sum_over_ranks(float(comp_bytes), comm_dev)
-        tokens_all = int(shard.sum_over_ranks(float(tokens_rank), comm_dev))
+        if args.full:
+            dec_s = shard.max_over_ranks(dec_s, comm_dev)
+            tokens_all = int(shard.sum_over_ranks(float(tokens_rank), comm_dev))
     else:
         comp_total = float(comp_bytes)
-        tokens_all = tokens_rank
+        if args.full:
+            tokens_all = tokens_rank
 
     # ---- N>1, strong: the same step with the batch starting and ending on rank 0 --------
     # (after every collective the device-local line needs: a failure here cannot take that line down).
@@ -400,7 +456,7 @@ def main():
     # collectives inside phase(); every phase ends with an all_reduce(MIN) of an ok flag, and once any
     # rank has failed ALL ranks skip the remaining collectives of the leg together.
     xfer = None
-    if world > 1 and strong and not args.no_transfer:
+    if args.full and world > 1 and strong and not args.no_transfer:
         state = {"ok": True, "why": ""}
 
         def phase(fn):
@@ -492,13 +548,6 @@ def main():
     if rank == 0:
         in_total = float(total_blocks) * bb
         ms_per_step = enc_s / args.steps * 1e3
-        enc_k = {k: v[0] / max(v[1], 1) for k, v in tim.items()}      # avg ms per launch
-        dec_k = {k: v[0] / max(v[1], 1) for k, v in dtim.items()}
-        dominant = max(enc_k, key=enc_k.get)
-        algo_bytes = n * bb + comp_bytes          # encode = n + c per block, this rank's launch
-        achieved = algo_bytes / (enc_k[dominant] * 1e-3) / 1e9
-        traffic, traffic_note = measured_traffic(dominant) if (world == 1 and n == 4096 and bb == 262144) \
-            else (None, "traffic is measured on the N=1 default workload only")
         if world == 1:
             scaling = "strong" if strong else "weak"
             workload = (f"{n} x {bb} B Zipf(s=1) byte blocks, window 2^{wb}, one independent stream per "
@@ -526,42 +575,52 @@ def main():
                        "parallelism": par,
                        "finder": args.finder,
                        "device": info["name"]},
-            "decode_MBps": round(in_total / dec_s * args.steps / 1e6, 3),
-            "decode_ms_per_step": round(dec_s / args.steps * 1e3, 3),
             "compressed_ratio": round(comp_total / in_total, 5),
-            "kernels_ms": {k: round(v, 3) for k, v in {**enc_k, **dec_k}.items()},
-            "roofline": {"bound": "hbm", "kernel": dominant,
-                         "achieved": round(achieved, 4), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 7), "traffic": traffic,
-                         "traffic_note": traffic_note,
-                         "algorithmic_bytes_per_launch": algo_bytes,
-                         "encode_frac_of_hbm_roof": round(
-                             algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 7)},
         }
-        if xfer is not None:
-            line["with_transfer"] = xfer
-        serial_ms = sum(enc_k.get(k, 0.0) for k in ("index_parse_kernel", "huffman_emit_kernel"))
-        sec = {
-            "note": "the path is a serial chain per stream, not HBM-bound: tokens through the "
-                    "adaptive-Huffman stage per second",
-            "tokens_per_step": tokens_all,
-            "tokens_per_s_encode": round(tokens_all / (ms_per_step * 1e-3), 1),
-            "tokens_per_s_emit_kernel": round(tokens_rank / (enc_k["huffman_emit_kernel"] * 1e-3), 1),
-            "tokens_per_s_entropy_decode_kernel": round(tokens_rank / (dec_k["entropy_decode_kernel"] * 1e-3), 1),
-            "serial_stage_ms": round(serial_ms, 3),
-        }
-        # the candidate tests the reference's O(window) scan makes for the same tokens (block 0 of
-        # this rank x its blocks).  Only --finder scan PERFORMS them; the indexed finder visits the
-        # equal-prefix candidates only, so for it the figure is what it avoids, not a rate it achieves.
-        cand = cand0 * total_blocks                 # block 0 of rank 0 stands for every block of the job
-        if args.finder == "scan":
-            sec["scan_candidate_tests_per_step"] = cand
-            sec["scan_candidate_tests_per_s"] = round(cand / (ms_per_step * 1e-3), 1)
-        else:
-            sec["reference_scan_candidate_tests_per_step_not_performed"] = cand
-        line["secondary"] = sec
-        if world == 1 and args.cpu_blocks > 0:
-            line["cpu_baseline"] = cpu_baseline(args.cpu_blocks, bb, wb)
+        if args.full:
+            enc_k = {k: v[0] / max(v[1], 1) for k, v in tim.items()}      # avg ms per launch
+            dec_k = {k: v[0] / max(v[1], 1) for k, v in dtim.items()}
+            dominant = max(enc_k, key=enc_k.get)
+            algo_bytes = n * bb + comp_bytes          # encode = n + c per block, this rank's launch
+            achieved = algo_bytes / (enc_k[dominant] * 1e-3) / 1e9
+            traffic, traffic_note = measured_traffic(dominant) if (world == 1 and n == 4096 and bb == 262144) \
+                else (None, "traffic is measured on the N=1 default workload only")
+            line.update({
+                "decode_MBps": round(in_total / dec_s * args.steps / 1e6, 3),
+                "decode_ms_per_step": round(dec_s / args.steps * 1e3, 3),
+                "kernels_ms": {k: round(v, 3) for k, v in {**enc_k, **dec_k}.items()},
+                "roofline": {"bound": "hbm", "kernel": dominant,
+                             "achieved": round(achieved, 4), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBPS, 7), "traffic": traffic,
+                             "traffic_note": traffic_note,
+                             "algorithmic_bytes_per_launch": algo_bytes,
+                             "encode_frac_of_hbm_roof": round(
+                                 algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS, 7)},
+            })
+            if xfer is not None:
+                line["with_transfer"] = xfer
+            serial_ms = sum(enc_k.get(k, 0.0) for k in ("index_parse_kernel", "huffman_emit_kernel"))
+            sec = {
+                "note": "the path is a serial chain per stream, not HBM-bound: tokens through the "
+                        "adaptive-Huffman stage per second",
+                "tokens_per_step": tokens_all,
+                "tokens_per_s_encode": round(tokens_all / (ms_per_step * 1e-3), 1),
+                "tokens_per_s_emit_kernel": round(tokens_rank / (enc_k["huffman_emit_kernel"] * 1e-3), 1),
+                "tokens_per_s_entropy_decode_kernel": round(tokens_rank / (dec_k["entropy_decode_kernel"] * 1e-3), 1),
+                "serial_stage_ms": round(serial_ms, 3),
+            }
+            # the candidate tests the reference's O(window) scan makes for the same tokens (block 0 of
+            # this rank x its blocks).  Only --finder scan PERFORMS them; the indexed finder visits the
+            # equal-prefix candidates only, so for it the figure is what it avoids, not a rate it achieves.
+            cand = cand0 * total_blocks                 # block 0 of rank 0 stands for every block of the job
+            if args.finder == "scan":
+                sec["scan_candidate_tests_per_step"] = cand
+                sec["scan_candidate_tests_per_s"] = round(cand / (ms_per_step * 1e-3), 1)
+            else:
+                sec["reference_scan_candidate_tests_per_step_not_performed"] = cand
+            line["secondary"] = sec
+            if world == 1 and args.cpu_blocks > 0:
+                line["cpu_baseline"] = cpu_baseline(args.cpu_blocks, bb, wb)
         print(json.dumps(line), flush=True)
 
     if world > 1:

@@ -12,7 +12,7 @@ rocprofv3 -L > $O/avail.txt 2>&1 || true
 i=0
 for set in $PMC_SETS; do
   i=$((i+1))
-  timeout -k 10 400 rocprofv3 --pmc ${set//,/ } --kernel-trace -d $O/pass$i -o p --output-format csv -- python $R/bench.py --steps 1 --warmup 0 --cpu-blocks 0 --no-verify ${BENCH_ARGS} > $O/pass$i.log 2>&1 || { echo "pass $i ($set) failed"; tail -3 $O/pass$i.log; }
+  timeout -k 10 400 rocprofv3 --pmc ${set//,/ } --kernel-trace -d $O/pass$i -o p --output-format csv -- python $R/bench.py --full --steps 1 --warmup 0 --cpu-blocks 0 --no-verify ${BENCH_ARGS} > $O/pass$i.log 2>&1 || { echo "pass $i ($set) failed"; tail -3 $O/pass$i.log; }
 done
 cd $R
 python - <<'PY'

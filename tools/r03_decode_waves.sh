@@ -11,7 +11,7 @@ for w in 4 2; do
 done
 for n in 512 1024 2048; do
   for w in 1 2 4; do
-    SQZ_DECODE_WAVES=$w timeout -k 10 200 python bench.py --steps 3 --warmup 1 --blocks $n --cpu-blocks 0 > $O/b${n}_w$w.log 2>&1 || { tail -5 $O/b${n}_w$w.log; exit 1; }
+    SQZ_DECODE_WAVES=$w timeout -k 10 200 python bench.py --full --steps 3 --warmup 1 --blocks $n --cpu-blocks 0 > $O/b${n}_w$w.log 2>&1 || { tail -5 $O/b${n}_w$w.log; exit 1; }
     grep '^{' $O/b${n}_w$w.log > $O/blocks_${n}_w$w.json
     python - <<PY
 import json

@@ -14,9 +14,9 @@ if [ "$PART" != "rc" ]; then bash /tmp/evidence_$TAG.sh || exit 1; fi
 O=$R/gpurun_out/rc_$TAG
 mkdir -p $O
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o p --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --codec rc --cpu-blocks 0 > $O/stats.log 2>&1 || { tail -5 $O/stats.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o p --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 --codec rc --cpu-blocks 0 > $O/stats.log 2>&1 || { tail -5 $O/stats.log; exit 1; }
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace -d $O/$c -o p --output-format csv -- python $R/bench.py --steps 1 --warmup 0 --codec rc --cpu-blocks 0 > $O/$c.log 2>&1 || { tail -5 $O/$c.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace -d $O/$c -o p --output-format csv -- python $R/bench.py --full --steps 1 --warmup 0 --codec rc --cpu-blocks 0 > $O/$c.log 2>&1 || { tail -5 $O/$c.log; exit 1; }
 done
 cd $R
 find $O/stats -name "*kernel_stats.csv" -exec cp {} gpurun_out/${TAG}_rc_kernel_stats.csv \;

@@ -9,7 +9,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_tree.
 grep -q "passed" $O/tests.txt && ! grep -q "failed" $O/tests.txt || exit 1
 timeout -k 10 120 python tools/microbench/time_stage1.py 2>&1 | tail -2 | tee $O/stage1.txt
 for n in 4096 512; do
-  timeout -k 10 200 python bench.py --steps 3 --warmup 1 --blocks $n --cpu-blocks 0 > $O/b$n.log 2>&1 || { tail -5 $O/b$n.log; exit 1; }
+  timeout -k 10 200 python bench.py --full --steps 3 --warmup 1 --blocks $n --cpu-blocks 0 > $O/b$n.log 2>&1 || { tail -5 $O/b$n.log; exit 1; }
   grep '^{' $O/b$n.log > $O/blocks_$n.json
 done
 python - <<PY
