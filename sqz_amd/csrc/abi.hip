@@ -317,7 +317,7 @@ void run_stage1(int finder, const uint8_t* d_in, const uint64_t* d_in_off, uint3
           // two arrays serve the three steps: the sort leaves the positions in work_a (work_m is its second
           // buffer), the match table goes to work_m (the sort is done with it), and the token words may take
           // work_a's place (tokens == work_a in the encode path: the sorted positions are dead by then)
-          sqzk::launch_index_sort(d_in, d_in_off, n, work_a, work_m /* ping-pong */, nullptr, slots, st); }
+          sqzk::launch_index_sort(d_in, d_in_off, n, work_a, work_m /* ping-pong */, slots, st); }
         { SpanGuard g(st, SQZ_HIP_K_INDEX_MATCH);
           sqzk::launch_index_match(d_in, d_in_off, n, window, work_a, work_m,
                                    match_groups_for(avg_block), slots, st); }

@@ -12,7 +12,8 @@
 //
 // Three kernels:
 //   index_sort_kernel   one 1024-thread workgroup per stream: stable LSD radix
-//                       sort (3 passes x 8 bits) of the positions 0..n-3 by their
+//                       sort (3 passes: 10 + 7 + 7 key bits for blocks of up to 256 KB,
+//                       8 + 8 + 8 for longer ones) of the positions 0..n-3 by their
 //                       3-byte prefix; the three histograms come from one sweep over
 //                       the bytes, every pass orders 4096-element tiles in LDS so that
 //                       a digit's elements leave as contiguous runs.  Equal prefixes
@@ -56,15 +57,24 @@ constexpr int kSortTile = 4 * kSortThreads;      // elements per workgroup tile 
 // later passes never gather a byte at random (those gathers were half of the kernel's 28.8 GB of
 // fetches: 64 streams of 256 KB per XCD against 4 MB of L2).  Longer blocks use 8 + 8 + 8: pass 1
 // gathers bytes p and p+1 and carries byte 0 (blocks up to 16 MB), pass 2 of longer ones gathers.
+//
+// A tile costs four workgroup barriers, and every thread works between any two of them: the waves rank
+// their own 256 elements (per-wave counters), ONE workgroup-wide exclusive scan over the bins x 16
+// counters in digit-major order turns every (wave, digit) counter into the tile slot of that wave's first
+// element of the digit (a thread owns 16, 4 or 2 counters of one digit), the elements go to their slots,
+// and the slots leave in order.  The barriers wait for LDS only: the tile's stores drain while the next
+// tile is ranked, and the next tile's loads are issued before this tile's ranking and consumed after its
+// copy-out, so no HBM round trip stands behind a barrier.  Only the pass boundary waits for the stores.
 constexpr int kSortBins = 1024;                  // most digits of a pass
+constexpr int kSortCntRow = kSortBins + 2;       // a wave's counters start one LDS bank after the wave's before (the scan reads a digit's 16 side by side)
 struct SortLds {
     uint32_t elem[kSortTile];                    // the tile in digit order
     uint16_t dig[kSortTile];                     // digit per tile slot
-    uint16_t cnt[kSortWaves][kSortBins];         // per tile: elements of (wave, digit) so far -> offset inside the digit's run
+    uint16_t cnt[kSortWaves][kSortCntRow];       // per tile: elements of (wave, digit) so far; after the scan: tile slot of the first of them
     uint32_t gbase[3][kSortBins];                // per pass: where the next tile's run of digit d goes
-    uint32_t tstart[kSortBins];                  // tile slot where digit d's run starts
-    uint32_t total[kSortBins];
-};                                               // 76 KB: two workgroups per CU
+    uint32_t delta[kSortBins];                   // per tile: (index in the pass's output) - (tile slot) of digit d's run
+    uint32_t wtot[kSortWaves];                   // the scan's hand-over: elements counted by each wave's threads
+};                                               // 72 KB: two workgroups per CU
 
 struct __attribute__((packed)) U32u { uint32_t v; };
 
@@ -72,23 +82,203 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) {
     return reinterpret_cast<const U32u*>(p)->v;
 }
 
-// lanes of this wave with the same digit (of `bits` bits) and valid, as a 64-bit mask
+// lanes of this wave with the same digit (of `bits` bits) and valid, as a 64-bit mask.  Per bit: the lane's bit spread
+// over a dword (one v_bfe_i32), one ballot, and per half of the mask an xnor and an and.
 __device__ __forceinline__ uint64_t peers_of(uint32_t digit, bool valid, int bits) {
-    uint64_t peers = __ballot(valid);
+    const uint64_t all = __ballot(valid);
+    uint32_t lo = (uint32_t)all, hi = (uint32_t)(all >> 32);
 #pragma unroll
     for (int bit = 0; bit < 10; bit++) {
         if (bit < bits) {
-            const bool set = (digit >> bit) & 1u;
-            const uint64_t m = __ballot(set);
-            peers &= set ? m : ~m;
+            const uint32_t mine = (uint32_t)((int32_t)(digit << (31 - bit)) >> 31);     // all ones: the bit is set
+            const uint64_t m = __ballot(mine != 0u);
+            lo &= ~((uint32_t)m ^ mine);                                                // set ? m : ~m
+            hi &= ~((uint32_t)(m >> 32) ^ mine);
         }
     }
-    return peers;
+    return ((uint64_t)hi << 32) | lo;
 }
 
 __device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {   // popcount of mask below this lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// the key of position k as one number: byte k first (most significant), byte k+2 last
+__device__ __forceinline__ uint32_t sort_key(const uint8_t* src, uint64_t bytes, uint32_t k) {
+    return (uint64_t)k + 4 <= bytes ? (__builtin_bswap32(load_u32_unaligned(src + k)) >> 8)
+                                    : (((uint32_t)src[k] << 16) | ((uint32_t)src[k + 1] << 8) | (uint32_t)src[k + 2]);
+}
+
+typedef uint32_t __attribute__((may_alias)) SortCntPair;      // two neighbouring uint16 counters, zeroed together
+
+// Section timers of the instrumented build (tools/build_stats.sh): cycles of wave 0 of block 1 per section, each
+// section including the barrier that ends it.  0 histogram sweep + bucket bases; per tile: 1 the tile's loads have
+// arrived (the instrumented build waits for them there: vmcnt(0), which also waits for the tile's stores before),
+// 2 rank, 3 scan (own counters), 4 scan (hand-over, slot bases), 5 place, 6 copy-out (issue only: no barrier).
+struct SortSec {
+#ifdef SQZ_STATS
+    uint64_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t last = 0;
+#endif
+};
+#ifdef SQZ_STATS
+#define SORT_SEC(s, k) { const uint64_t n_ = __builtin_readcyclecounter(); (s).t[k] += n_ - (s).last; (s).last = n_; }
+#define SORT_SEC_LOADS(s, k) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); SORT_SEC(s, k) }
+#else
+#define SORT_SEC(s, k)
+#define SORT_SEC_LOADS(s, k)
+#endif
+
+// One pass: the elements of `from` (pass 0: the positions in order), by the pass's digit of kBits bits, to `to`.
+// kSmall: the 10 + 7 + 7 split of blocks up to 256 KB (kBits == 10 is its pass 0); else 8 + 8 + 8.
+template <int kBits, bool kSmall>
+__device__ __forceinline__ void sort_pass(SortLds& lds, const int pass, const uint8_t* __restrict__ src,
+                                          const uint64_t bytes, const uint32_t count, const bool carry,
+                                          const uint32_t* __restrict__ from, uint32_t* __restrict__ to, SortSec& sec) {
+    constexpr int kDigits = 1 << kBits;
+    constexpr int kTpd = kSortThreads / kDigits;       // the scan: threads per digit (1, 8 or 4) ...
+    constexpr int kWpt = kSortWaves / kTpd;            // ... and waves' counters per thread (16, 2 or 4)
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool first = kSmall ? kBits == 10 : pass == 0;
+    uint32_t* const gbase = lds.gbase[pass];
+
+    // element k of the input order belongs to tile k / 4096, wave (k / 256) % 16, row (k / 64) % 4.
+    // What a tile needs from memory, one dword per row: the key (pass 0) or the element.
+    // Every lane loads, from a clamped address, so that the four loads are issued back to back with nothing waiting
+    // on them: a row past the end reads the last element again and is not used.  Pass 0 reads the dword at k, whose
+    // first three bytes are the key; the last position has no fourth byte and reads the dword one byte earlier
+    // (bytes >= 4: the kernel deals with a 3-byte block by itself).
+    auto fetch = [&](uint32_t tile, uint32_t (&raw)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t k = tile + (uint32_t)(wave * 256 + j * kWave + lane);
+            if (first) {
+                const uint32_t last = (uint32_t)(bytes - 4);
+                raw[j] = load_u32_unaligned(src + (k < last ? k : last));
+            } else {
+                raw[j] = from[k < count ? k : count - 1u];
+            }
+        }
+    };
+    auto key_from = [&](uint32_t raw, uint32_t k) {
+        const uint32_t be = __builtin_bswap32(raw);
+        return (uint64_t)k + 4 <= bytes ? be >> 8 : be & 0x00FFFFFFu;
+    };
+    auto decode = [&](uint32_t tile, const uint32_t (&raw)[4], uint32_t (&elem)[4], uint32_t (&digit)[4], bool (&valid)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t k = tile + (uint32_t)(wave * 256 + j * kWave + lane);
+            valid[j] = k < count;
+            const uint32_t pos = valid[j] ? (first ? k : raw[j]) : 0u;
+            digit[j] = 0; elem[j] = pos;
+            if (!valid[j]) { continue; }
+            if (kSmall) {
+                if (first) {
+                    const uint32_t key = key_from(raw[j], k);
+                    digit[j] = key & 0x3FFu;
+                    elem[j] = pos | ((key >> 10) << 18);                 // 14 key bits above an 18-bit position
+                } else if (pass == 1) {
+                    digit[j] = (pos >> 18) & 0x7Fu;
+                } else {
+                    digit[j] = pos >> 25;
+                    elem[j] = pos & 0x3FFFFu;
+                }
+            } else if (first) {
+                digit[j] = key_from(raw[j], k) & 0xFFu;                  // byte k+2
+            } else if (pass == 1) {                                      // the one random gather: bytes p and p+1
+                const uint32_t w = (uint32_t)src[pos] | ((uint32_t)src[pos + 1] << 8);
+                digit[j] = w >> 8;
+                if (carry) { elem[j] = pos | ((w & 0xFFu) << 24); }
+            } else {
+                digit[j] = carry ? (pos >> 24) : (uint32_t)src[pos];
+                if (carry) { elem[j] = pos & 0x00FFFFFFu; }
+            }
+        }
+    };
+
+    // A tile's dwords are loaded one tile ahead and turned into elements and digits at the END of the tile before, behind
+    // that tile's stores: the wait is for the four loads in front of the stores, and no wave ever waits for a store.
+    uint32_t ahead[4], elem[4], digit[4], wrank[4];
+    bool valid[4];
+    fetch(0u, ahead);
+    decode(0u, ahead, elem, digit, valid);
+    SORT_SEC_LOADS(sec, 1)
+    for (uint32_t tile = 0; tile < count; tile += (uint32_t)kSortTile) {
+        const uint32_t n_tile = count - tile < (uint32_t)kSortTile ? count - tile : (uint32_t)kSortTile;
+        fetch(tile + (uint32_t)kSortTile, ahead);          // (past the last tile: the last element, four times)
+        {   // this wave's counters: nobody else looks at them between the last barrier of a tile and the first of the next
+            SortCntPair* const row = reinterpret_cast<SortCntPair*>(lds.cnt[wave]);
+            for (int d = lane; d < kDigits / 2; d += kWave) { row[d] = 0u; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {                      // rows in order: stability
+            const uint64_t peers = peers_of(digit[j], valid[j], kBits);
+            const uint32_t rank = lanes_below(peers);
+            wrank[j] = valid[j] ? (uint32_t)lds.cnt[wave][digit[j]] + rank : 0u;
+            __builtin_amdgcn_wave_barrier();               // all reads before the leaders' writes
+            if (valid[j] && rank == 0) {
+                lds.cnt[wave][digit[j]] = (uint16_t)(lds.cnt[wave][digit[j]] + (uint32_t)__builtin_popcountll(peers));
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        lds_barrier();
+        SORT_SEC(sec, 2)
+        // exclusive scan over the counters in (digit, wave) order: thread t owns kWpt waves' counters of one digit
+        const int sd = tid / kTpd;
+        const int sw = (tid % kTpd) * kWpt;
+        uint32_t c[kWpt], sum = 0;
+#pragma unroll
+        for (int i = 0; i < kWpt; i++) { c[i] = lds.cnt[sw + i][sd]; sum += c[i]; }
+        const uint32_t incl = wave_scan(sum);
+        if (lane == kWave - 1) { lds.wtot[wave] = incl; }
+        lds_barrier();
+        SORT_SEC(sec, 3)
+        uint32_t at = wave_scan(lane < wave ? lds.wtot[lane] : 0u);          // the waves in front of this one
+        at = (uint32_t)__builtin_amdgcn_readlane((int)at, kWave - 1) + incl - sum;
+        const uint32_t run = at;                           // (of the digit's first thread: where its run starts in the tile)
+#pragma unroll
+        for (int i = 0; i < kWpt; i++) { lds.cnt[sw + i][sd] = (uint16_t)at; at += c[i]; }
+        const uint32_t run_end = kTpd > 1 ? (uint32_t)__shfl((int)at, lane | (kTpd - 1)) : at;
+        if (tid % kTpd == 0) {                             // the run's place in the output, and the next tile's
+            const uint32_t g = gbase[sd];
+            lds.delta[sd] = g - run;
+            gbase[sd] = g + (run_end - run);
+        }
+        lds_barrier();
+        SORT_SEC(sec, 4)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (valid[j]) {
+                const uint32_t slot = (uint32_t)lds.cnt[wave][digit[j]] + wrank[j];
+                if (slot < (uint32_t)kSortTile) {          // always: slots are a permutation of [0, n_tile)
+                    lds.elem[slot] = elem[j];
+                    lds.dig[slot] = (uint16_t)digit[j];
+                }
+            }
+        }
+        lds_barrier();
+        SORT_SEC(sec, 5)
+        // Runs leave contiguously.  Every lane stores, so that the four stores are issued back to back and what follows
+        // can tell them from the loads in front of them: a slot past the tile's end stores the tile's last element
+        // again, and the clamp never acts (slot -> index is a permutation of [0, count)): it only keeps a store inside
+        // the stream's array whatever the counters hold.
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t slot = (uint32_t)(j * kSortThreads + tid);
+            const uint32_t s = slot < n_tile ? slot : n_tile - 1u;
+            const uint32_t dest = s + lds.delta[lds.dig[s]];
+            to[dest < count ? dest : count - 1u] = lds.elem[s];
+        }
+        SORT_SEC(sec, 6)
+        decode(tile + (uint32_t)kSortTile, ahead, elem, digit, valid);
+        SORT_SEC_LOADS(sec, 1)
+    }
+    // the next pass reads what other waves of this workgroup wrote
+    __threadfence_block();
+    __syncthreads();
 }
 
 __global__ __launch_bounds__(kSortThreads)
@@ -97,7 +287,6 @@ void index_sort_kernel(const uint8_t* __restrict__ in,
                        uint32_t n_blocks,
                        uint32_t* __restrict__ buf_a,      // result lands here
                        uint32_t* __restrict__ buf_b,
-                       uint32_t* __restrict__ tmp,        // 4 bytes per position of scratch
                        uint64_t slots) {
     __shared__ SortLds lds;
     const uint32_t b = blockIdx.x;
@@ -112,27 +301,43 @@ void index_sort_kernel(const uint8_t* __restrict__ in,
     const uint32_t count = (uint32_t)(bytes - 2);             // positions with a 3-byte prefix
     uint32_t* const pa = buf_a + in_off[b];
     uint32_t* const pb = buf_b + in_off[b];
-    (void)tmp;                                                // (was the per-row byte cache of the counting sweeps)
-    // the key of position k as one number: byte k first (most significant), byte k+2 last
-    auto key_of = [&](uint32_t k) {
-        return (uint64_t)k + 4 <= bytes ? (__builtin_bswap32(load_u32_unaligned(src + k)) >> 8)
-                                        : (((uint32_t)src[k] << 16) | ((uint32_t)src[k + 1] << 8) | (uint32_t)src[k + 2]);
-    };
+    if (bytes == 3) {                                         // one position (and no dword to read its key from)
+        if (tid == 0) { pa[0] = 0u; }
+        return;
+    }
     const bool small = bytes <= (1u << 18);                   // the unsorted key bits fit above the position
     const bool carry = bytes <= (1u << 24);                   // (8 + 8 + 8) byte 0 fits above the position
     // pass p sorts by key bits [shift[p], shift[p] + width[p])
     const int w0 = small ? 10 : 8, w1 = small ? 7 : 8, w2 = small ? 7 : 8;
     const int s1 = w0, s2 = w0 + w1;
     const uint32_t m0 = (1u << w0) - 1u, m1 = (1u << w1) - 1u;
+    SortSec sec;
+#ifdef SQZ_STATS
+    sec.last = __builtin_readcyclecounter();
+    const uint64_t sec_begin = sec.last;
+#endif
     // ---- all three histograms from the bytes ------------------------------------------------
     for (int d = tid; d < 3 * kSortBins; d += kSortThreads) { (&lds.gbase[0][0])[d] = 0; }
     __syncthreads();
-    for (uint32_t k = (uint32_t)tid; k < count; k += (uint32_t)kSortThreads) {
-        const uint32_t key = key_of(k);
+    // a thread takes four neighbouring positions from two dwords, the next two already in flight; the few positions
+    // after the last whole quad (its 7 bytes must exist) go one by one
+    auto count_key = [&](uint32_t key) {
         atomicAdd(&lds.gbase[0][key & m0], 1u);
         atomicAdd(&lds.gbase[1][(key >> s1) & m1], 1u);
         atomicAdd(&lds.gbase[2][key >> s2], 1u);
+    };
+    const uint32_t quads = bytes >= 8 ? (uint32_t)((bytes - 8) / 4) + 1u : 0u;
+    if ((uint32_t)tid < quads) {
+        uint32_t lo = load_u32_unaligned(src + 4u * (uint32_t)tid), hi = load_u32_unaligned(src + 4u * (uint32_t)tid + 4u);
+        for (uint32_t q = (uint32_t)tid; q < quads; q += (uint32_t)kSortThreads) {
+            const uint64_t eight = ((uint64_t)hi << 32) | lo;
+            const uint32_t nq = q + (uint32_t)kSortThreads < quads ? q + (uint32_t)kSortThreads : q;
+            lo = load_u32_unaligned(src + 4u * nq); hi = load_u32_unaligned(src + 4u * nq + 4u);
+#pragma unroll
+            for (int j = 0; j < 4; j++) { count_key(__builtin_bswap32((uint32_t)(eight >> (8 * j))) >> 8); }
+        }
     }
+    for (uint32_t k = 4u * quads + (uint32_t)tid; k < count; k += (uint32_t)kSortThreads) { count_key(sort_key(src, bytes, k)); }
     __syncthreads();
     if (wave < 3) {                                        // exclusive scans: counts -> bases
         uint32_t* const g = lds.gbase[wave];
@@ -143,116 +348,27 @@ void index_sort_kernel(const uint8_t* __restrict__ in,
         for (int j = 0; j < per; j++) { const uint32_t v = g[per * lane + j]; g[per * lane + j] = excl; excl += v; }
     }
     __syncthreads();
+    SORT_SEC(sec, 0)
 
-    for (int pass = 0; pass < 3; pass++) {
-        // pass 0: identity -> A ; pass 1: A -> B ; pass 2: B -> A
-        const uint32_t* from = pass == 1 ? pa : pb;
-        uint32_t* to = pass == 1 ? pb : pa;
-        uint32_t* const gbase = lds.gbase[pass];
-        const int bits = pass == 0 ? w0 : pass == 1 ? w1 : w2;
-        const int bins = 1 << bits;
-
-        // element k of the input order belongs to tile k / 4096, wave (k / 256) % 16, row (k / 64) % 4
-        auto load_rows = [&](uint32_t tile, uint32_t (&elem)[4], uint32_t (&digit)[4], bool (&valid)[4]) {
-            uint32_t pos[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint32_t k = tile + (uint32_t)(wave * 256 + j * kWave + lane);
-                valid[j] = k < count;
-                pos[j] = valid[j] ? (pass == 0 ? k : from[k]) : 0u;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                digit[j] = 0; elem[j] = pos[j];
-                if (!valid[j]) { continue; }
-                if (small) {
-                    if (pass == 0) {
-                        const uint32_t key = key_of(pos[j]);
-                        digit[j] = key & m0;
-                        elem[j] = pos[j] | ((key >> 10) << 18);          // 14 key bits above an 18-bit position
-                    } else if (pass == 1) {
-                        digit[j] = (pos[j] >> 18) & m1;
-                    } else {
-                        digit[j] = pos[j] >> 25;
-                        elem[j] = pos[j] & 0x3FFFFu;
-                    }
-                } else if (pass == 0) {
-                    digit[j] = src[pos[j] + 2];
-                } else if (pass == 1) {                              // the one random gather: bytes p and p+1
-                    const uint32_t w = (uint32_t)src[pos[j]] | ((uint32_t)src[pos[j] + 1] << 8);
-                    digit[j] = w >> 8;
-                    if (carry) { elem[j] = pos[j] | ((w & 0xFFu) << 24); }
-                } else {
-                    digit[j] = carry ? (pos[j] >> 24) : (uint32_t)src[pos[j]];
-                    if (carry) { elem[j] = pos[j] & 0x00FFFFFFu; }
-                }
-            }
-        };
-
-        // ---- scatter, tile by tile ------------------------------------------------------
-        for (uint32_t tile = 0; tile < count; tile += (uint32_t)kSortTile) {
-            const uint32_t n_tile = count - tile < (uint32_t)kSortTile ? count - tile : (uint32_t)kSortTile;
-            for (int d = lane; d < bins; d += kWave) { lds.cnt[wave][d] = 0; }
-            uint32_t elem[4], digit[4], wrank[4];
-            bool valid[4];
-            load_rows(tile, elem, digit, valid);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {                      // rows in order: stability
-                const uint64_t peers = peers_of(digit[j], valid[j], bits);
-                const uint32_t rank = lanes_below(peers);
-                wrank[j] = valid[j] ? (uint32_t)lds.cnt[wave][digit[j]] + rank : 0u;
-                __builtin_amdgcn_wave_barrier();               // all reads before the leaders' writes
-                if (valid[j] && rank == 0) {
-                    lds.cnt[wave][digit[j]] = (uint16_t)(lds.cnt[wave][digit[j]] + (uint32_t)__builtin_popcountll(peers));
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-            __syncthreads();
-            uint32_t tcount = 0;
-            if (tid < bins) {                                  // offsets of the waves inside a digit's run
-                for (int w = 0; w < kSortWaves; w++) {
-                    const uint32_t c = lds.cnt[w][tid];
-                    lds.cnt[w][tid] = (uint16_t)tcount;
-                    tcount += c;
-                }
-                lds.total[tid] = tcount;
-            }
-            __syncthreads();
-            if (wave == 0) {                                   // where each digit's run starts in the tile
-                const int per = bins / kWave;
-                uint32_t sum = 0;
-                for (int j = 0; j < per; j++) { sum += lds.total[per * lane + j]; }
-                uint32_t excl = wave_scan(sum) - sum;
-                for (int j = 0; j < per; j++) { lds.tstart[per * lane + j] = excl; excl += lds.total[per * lane + j]; }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                if (valid[j]) {
-                    const uint32_t slot = lds.tstart[digit[j]] + (uint32_t)lds.cnt[wave][digit[j]] + wrank[j];
-                    if (slot < (uint32_t)kSortTile) {          // always: slots are a permutation of [0, n_tile)
-                        lds.elem[slot] = elem[j];
-                        lds.dig[slot] = (uint16_t)digit[j];
-                    }
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 4; j++) {                      // runs leave contiguously
-                const uint32_t slot = (uint32_t)(j * kSortThreads + tid);
-                if (slot < n_tile) {
-                    const uint32_t d = lds.dig[slot];
-                    const uint32_t dest = gbase[d] + (slot - lds.tstart[d]);
-                    if (dest < count) { to[dest] = lds.elem[slot]; }   // always: a permutation of [0, count)
-                }
-            }
-            __syncthreads();
-            if (tid < bins) { gbase[tid] += tcount; }
+    // pass 0: identity -> A ; pass 1: A -> B ; pass 2: B -> A
+    if (small) {
+        sort_pass<10, true>(lds, 0, src, bytes, count, carry, pb, pa, sec);
+        for (int pass = 1; pass < 3; pass++) {
+            sort_pass<7, true>(lds, pass, src, bytes, count, carry, pass == 1 ? pa : pb, pass == 1 ? pb : pa, sec);
         }
-        // the next pass reads what other waves of this workgroup wrote
-        __threadfence_block();
-        __syncthreads();
+    } else {
+        for (int pass = 0; pass < 3; pass++) {
+            sort_pass<8, false>(lds, pass, src, bytes, count, carry, pass == 1 ? pa : pb, pass == 1 ? pb : pa, sec);
+        }
     }
+#ifdef SQZ_STATS
+    if (tid == 0 && b == 1) {
+        printf("sort block 1: cycles %llu: hist %llu; tiles: loads %llu rank %llu scan_a %llu scan_b %llu place %llu copy_out %llu\n",
+               (unsigned long long)(sec.last - sec_begin), (unsigned long long)sec.t[0], (unsigned long long)sec.t[1],
+               (unsigned long long)sec.t[2], (unsigned long long)sec.t[3], (unsigned long long)sec.t[4],
+               (unsigned long long)sec.t[5], (unsigned long long)sec.t[6]);
+    }
+#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -630,11 +746,11 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
 }
 
 void launch_index_sort(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
-                       uint32_t* buf_a, uint32_t* buf_b, uint32_t* tmp, uint64_t slots,
+                       uint32_t* buf_a, uint32_t* buf_b, uint64_t slots,
                        hipStream_t stream) {
     if (n_blocks == 0) { return; }
     hipLaunchKernelGGL(index_sort_kernel, dim3(n_blocks), dim3(kSortThreads), 0, stream,
-                       in, in_off, n_blocks, buf_a, buf_b, tmp, slots);
+                       in, in_off, n_blocks, buf_a, buf_b, slots);
 }
 
 void launch_index_match(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,

@@ -24,7 +24,7 @@ void launch_lz77_scan(const uint8_t* in, const uint64_t* in_off, uint32_t n_bloc
 // distance (lz77_index.hip): sort -> match -> parse.  buf_a / buf_b / match: one
 // uint32 slot per input byte each, addressed like `tokens`.
 void launch_index_sort(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
-                       uint32_t* buf_a, uint32_t* buf_b, uint32_t* tmp, uint64_t slots,
+                       uint32_t* buf_a, uint32_t* buf_b, uint64_t slots,
                        hipStream_t stream);
 void launch_index_match(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
                         uint32_t window, const uint32_t* sorted, uint32_t* match,
