@@ -5,7 +5,7 @@
  * and sizes; no HIP or torch types appear in any signature (streams and device
  * pointers travel as void*).
  *
- * Three layers, all backed by the same HIP kernels (there is NO CPU fallback:
+ * Four layers, all backed by the same HIP kernels (there is NO CPU fallback:
  * every entry point reports ENODEV when no gfx950 device can be opened):
  *
  *  1. single-stream API with the reference's documented names
@@ -19,9 +19,12 @@
  *     attic harness (attic/map_experiment/test.c:54-61,114-134)
  *  3. batch API over independent blocks -- the data-parallel hot path:
  *     host-buffer flavour and device-resident flavour (what bench.py times).
+ *  4. SQZF frames: one checksummed, seekable artifact for one large buffer, built from
+ *     layer 3's streams (this project's container, not the reference's; see below).
  *
  * Errors are the reference's sticky errno integers (squeeze.h:82,224-237;
- * bitstream.h:15,38,74): 0, EINVAL, E2BIG, ENOMEM; plus ENODEV (no GPU).
+ * bitstream.h:15,38,74): 0, EINVAL, E2BIG, ENOMEM; plus ENODEV (no GPU) and, for frames,
+ * EILSEQ (a checksum does not match).
  */
 #ifndef SQZ_AMD_SQZ_H
 #define SQZ_AMD_SQZ_H
@@ -312,6 +315,101 @@ SQZ_API int sqz_hip_pack_blocks(const void* d_slabs, const uint64_t* d_slab_off,
                                 void* d_dense, const uint64_t* d_dense_off,
                                 uint64_t avg_bytes, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* SQZF: a checksummed, seekable frame around the block streams -- ONE artifact for one large
+ * buffer, decodable without side information.  This is THIS PROJECT'S format, not the
+ * reference's ("block size is part of the format the build defines"); the
+ * streams inside are exactly what sqz_encode_blocks produces, bit-identical to the reference's
+ * squeeze_compress output for each block without its 72-bit header.  Version 1, all integers
+ * little-endian:
+ *
+ *   offset  size  field
+ *   0       4     magic  53 51 5A 46  ("SQZF")
+ *   4       1     version = 1
+ *   5       1     win_bits      10..15  (window = 1 << win_bits for every block)
+ *   6       1     block_bits    12..24  (block_bytes = 1 << block_bits)
+ *   7       1     flags = 0     (a reader refuses any other value)
+ *   8       8     content_bytes           uncompressed length
+ *   16      8     payload_bytes           sum of all stream lengths
+ *   24      4     n_blocks = ceil(content_bytes / block_bytes)   (0 for empty content)
+ *   28      4     index_crc     CRC-32 over bytes [0,28) followed by the whole index
+ *   32      8*n   index: per block { u32 stream_words ; u32 content_crc }
+ *   ..            zero padding to the next multiple of 16  -> payload_off
+ *   payload_off   the n streams back to back, stream b is stream_words[b] * 8 bytes
+ *
+ * Block b covers content bytes [b * block_bytes, min((b+1) * block_bytes, content_bytes)).
+ * content_crc is the CRC-32 of the block's uncompressed bytes as zlib's crc32 computes it (IEEE
+ * 802.3, reflected polynomial 0xEDB88320, initial value and final xor 0xFFFFFFFF); index_crc is
+ * the same function.  frame_bytes = payload_off + payload_bytes: 32 for empty content.
+ *
+ * Errors: EINVAL a malformed header or argument, EILSEQ a checksum that does not match, E2BIG
+ * a buffer (avail, capacity) that is too small.                                             */
+enum {
+    sqz_frame_header_bytes   = 32,
+    sqz_frame_min_block_bits = 12,
+    sqz_frame_max_block_bits = 24
+};
+struct sqz_frame_info {
+    uint64_t content_bytes, payload_bytes, payload_off, frame_bytes, block_bytes;
+    uint32_t n_blocks, win_bits, version, reserved;
+};
+
+/* Host code, no device is touched (like sqz_file_words). */
+/* worst-case frame_bytes: header + index + padding + sqz_bound per block; 0 for a block_bits
+ * outside 12..24 */
+SQZ_API uint64_t sqz_frame_bound(uint64_t content_bytes, uint32_t block_bits);
+/* Parses and checks the header from the first `avail` bytes (E2BIG when avail < 32): magic,
+ * version, flags, the ranges of win_bits / block_bits, n_blocks == ceil(content_bytes /
+ * block_bytes), no overflow in 32 + 8n or frame_bytes (EINVAL).  When avail also covers the
+ * index: index_crc (EILSEQ), and that the stream_words sum to payload_bytes / 8 (EINVAL).   */
+SQZ_API int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* out);
+
+/* Host buffers in, host buffers out (H2D + kernels + D2H inside, on a leased lane's stream).
+ * The encode scratch is 8 bytes per input byte, so both directions work through the buffer in
+ * PASSES of whole blocks, at most 1 GiB of content each (SQZ_FRAME_PASS_BYTES overrides; one
+ * block at least), and still produce / consume one frame.
+ * compress: E2BIG when `capacity` is too small; *frame_bytes is the size needed either way and
+ *   nothing is written beyond capacity.
+ * decompress: accepts avail >= frame_bytes (a frame may be followed by another record).
+ *   Returns 0 only when every block decoded and every checksum matched.  block_err (optional,
+ *   n_blocks entries): a block whose stream the decoder rejects keeps the decoder's errno, one
+ *   that decodes to the wrong bytes gets EILSEQ; the call returns the first non-zero one.  Good
+ *   blocks are still delivered.  E2BIG when capacity < content_bytes or avail < frame_bytes.
+ * read: content bytes [offset, offset + length) -> out.  Uploads and decodes only the covering
+ *   blocks (plus header and index), verifies their checksums, copies back only the range.
+ *   EINVAL when the range leaves the content.                                               */
+SQZ_API int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                               uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes);
+SQZ_API int sqz_frame_decompress(const uint8_t* frame, uint64_t avail, uint8_t* data, uint64_t capacity,
+                                 uint64_t* bytes, int32_t* block_err);
+SQZ_API int sqz_frame_read(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length,
+                           uint8_t* out);
+
+/* Device-resident flavour: every pointer a DEVICE pointer (d_frame 16-byte aligned), asynchronous,
+ * no host synchronisation inside.  The stream sizes are only known on the device, so the prefix
+ * sum, the index, payload_bytes, index_crc and the compaction of the slabs all happen in kernels.
+ * encode: *d_frame_bytes (u64) = the size needed; *d_status (i32) = 0, E2BIG when that exceeds
+ *   `capacity` (nothing is written to d_frame then), or the first failed block's errno; d_err has
+ *   n_blocks = ceil(content_bytes >> block_bits) entries.
+ * decode: n_blocks and content_bytes are what sqz_frame_info said about a host copy of the 32
+ *   header bytes; avail must cover header and index (E2BIG at the call otherwise).  A kernel checks
+ *   that the device header agrees, index_crc, the stream_words sum and that the payload lies inside
+ *   avail.  If any of that fails *d_status is set (EINVAL / EILSEQ / E2BIG), every d_err[b] gets
+ *   the same value and no kernel reads the payload or writes d_out: a corrupt frame is refused by
+ *   arithmetic.  Otherwise d_err[b] as for sqz_frame_decompress.  d_out holds content_bytes.    */
+SQZ_API uint64_t sqz_hip_frame_scratch_bytes(uint64_t content_bytes, uint32_t block_bits, int encode);
+SQZ_API int sqz_hip_frame_encode(const void* d_in, uint64_t content_bytes, uint32_t win_bits,
+                                 uint32_t block_bits, void* d_frame, uint64_t capacity,
+                                 uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err,
+                                 void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API int sqz_hip_frame_decode(const void* d_frame, uint64_t avail, uint32_t n_blocks,
+                                 uint64_t content_bytes, void* d_out, int32_t* d_err, int32_t* d_status,
+                                 void* d_scratch, uint64_t scratch_bytes, void* stream);
+/* The checksum kernel on its own: d_crc[b] = CRC-32 (zlib) of d_in[d_in_off[b] .. d_in_off[b+1]),
+ * n ragged ranges at arbitrary (unaligned) offsets; n + 1 offsets, n results.               */
+SQZ_API int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n,
+                                 uint32_t* d_crc, void* stream);
+
 /* which finder sqz_compress / sqz_*encode_blocks use: 1 = indexed (default),
  * 0 = brute-force scan; also settable with SQZ_FINDER=scan|index.           */
 SQZ_API void sqz_hip_set_finder(int finder);
@@ -330,6 +428,8 @@ enum {
     SQZ_HIP_K_LZ_EXPAND = 6,      /* lz_expand_kernel                                 */
     SQZ_HIP_K_RC_ENCODE = 7,      /* rc_encode_kernel  } R-era range coder            */
     SQZ_HIP_K_RC_DECODE = 8,      /* rc_decode_kernel  } (include/sqz/sqz_rc.h)       */
+    SQZ_HIP_K_CRC32 = 9,          /* crc32_blocks_kernel } SQZF frames                */
+    SQZ_HIP_K_FRAME_INDEX = 10,   /* frame_index_kernel / frame_open_kernel }         */
     SQZ_HIP_KERNELS = 12
 };
 typedef struct sqz_hip_timing {

@@ -9,4 +9,14 @@ from .codec import (SqzError, bound, compress, decompress, device_info,  # noqa:
                     file_words, MIN_WIN_BITS, MAX_WIN_BITS)
 
 __all__ = ["SqzError", "bound", "compress", "decompress", "device_info", "file_words",
-           "MIN_WIN_BITS", "MAX_WIN_BITS"]
+           "MIN_WIN_BITS", "MAX_WIN_BITS", "compress_frame", "decompress_frame", "frame_info", "read_range"]
+
+_FRAME = ("compress_frame", "decompress_frame", "frame_info", "read_range")
+
+
+def __getattr__(name):
+    # SQZF frames (sqz_amd/frame.py), loaded on first use so that `python -m sqz_amd.frame` runs it once
+    if name in _FRAME:
+        from . import frame
+        return getattr(frame, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -29,7 +29,8 @@ class Sqz(C.Structure):
 
 KERNEL_NAMES = ["lz77_scan_kernel", "huffman_emit_kernel", "entropy_decode_kernel",
                 "index_sort_kernel", "index_match_kernel", "index_parse_kernel",
-                "lz_expand_kernel", "rc_encode_kernel", "rc_decode_kernel", "reserved", "reserved", "reserved"]
+                "lz_expand_kernel", "rc_encode_kernel", "rc_decode_kernel", "crc32_blocks_kernel",
+                "frame_index_kernel", "reserved"]
 
 
 class BlockStats(C.Structure):
@@ -52,6 +53,13 @@ RangeCoder._fields_ = [("low", C.c_uint64), ("range", C.c_uint64), ("code", C.c_
 class SqzRc(C.Structure):
     """struct sqz_rc of include/sqz/sqz_rc.h (struct sqz at HEAD, inc/sqz/sqz.h:69-79)."""
     _fields_ = [("rc", RangeCoder), ("that", C.c_void_p), ("reserved", C.c_uint64 * 8)]
+
+
+class FrameInfo(C.Structure):
+    """struct sqz_frame_info of include/sqz/sqz.h: what the header of an SQZF frame says."""
+    _fields_ = [(n, C.c_uint64) for n in ("content_bytes", "payload_bytes", "payload_off", "frame_bytes",
+                                          "block_bytes")] + \
+               [(n, C.c_uint32) for n in ("n_blocks", "win_bits", "version", "reserved")]
 
 
 class Timing(C.Structure):
@@ -112,6 +120,17 @@ PROTOTYPES = {
     "sqz_rc_bound": (C.c_uint64, [C.c_uint64]),
     "sqz_hip_rc_encode_blocks": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "sqz_hip_rc_decode_blocks": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sqz_frame_bound": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "sqz_frame_info": (C.c_int, [_vp, C.c_uint64, C.POINTER(FrameInfo)]),
+    "sqz_frame_compress": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u64p]),
+    "sqz_frame_decompress": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
+    "sqz_frame_read": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp]),
+    "sqz_hip_frame_scratch_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_int]),
+    "sqz_hip_frame_encode": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp,
+                                       _vp, C.c_uint64, _vp]),
+    "sqz_hip_frame_decode": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64,
+                                       _vp]),
+    "sqz_hip_crc32_blocks": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "sqz_hip_set_finder": (None, [C.c_int]),
     "sqz_hip_get_finder": (C.c_int, []),
     "sqz_hip_set_timing": (None, [C.c_int]),

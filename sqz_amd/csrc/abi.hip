@@ -56,8 +56,9 @@ Ctx& ctx() { static Ctx c; return c; }
 // different lanes, so two threads neither serialise on a lock nor share the NULL stream.
 struct Lane {
     hipStream_t own = nullptr;      // created with the lane (non-blocking: independent of the NULL stream)
+    int device = -1;                // hipGetDevice() when the lane was made: its buffers and stream live there
     DevBuf in, out, in_off, out_off, tokens, tok_count, out_bytes, err, end_bit, work_a, work_m,
-           dense, dense_off;
+           dense, dense_off, crc, misc;
     std::vector<uint8_t> host_dense;   // landing area of the host flavour's one device-to-host copy
 };
 
@@ -72,12 +73,18 @@ struct LaneLease {
     Lane* lane = nullptr;
     LaneLease() {
         LanePool& p = lanes();
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess) { dev = -1; }
         {
+            // only a lane of the CURRENT device: another device's buffers and stream are of no use here
             std::lock_guard<std::mutex> g(p.mu);
-            if (!p.idle.empty()) { lane = p.idle.back(); p.idle.pop_back(); }
+            for (size_t k = p.idle.size(); k-- > 0;) {
+                if (p.idle[k]->device == dev) { lane = p.idle[k]; p.idle.erase(p.idle.begin() + (long)k); break; }
+            }
         }
         if (lane == nullptr) {
             lane = new Lane();
+            lane->device = dev;
             if (hipStreamCreateWithFlags(&lane->own, hipStreamNonBlocking) != hipSuccess) { lane->own = nullptr; }
             p.made.fetch_add(1);
         }
@@ -446,6 +453,197 @@ int decode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_o
     }
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+
+// ---------------------------------------------------------------- SQZF frames (include/sqz/sqz.h)
+static_assert(EINVAL == 22 && E2BIG == 7 && EILSEQ == 84, "frame.hip writes these errno values from the device");
+
+uint32_t get_le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+uint64_t get_le64(const uint8_t* p) { return (uint64_t)get_le32(p) | ((uint64_t)get_le32(p + 4) << 32); }
+void put_le32(uint8_t* p, uint32_t v) { for (int k = 0; k < 4; k++) { p[k] = (uint8_t)(v >> (8 * k)); } }
+void put_le64(uint8_t* p, uint64_t v) { put_le32(p, (uint32_t)v); put_le32(p + 4, (uint32_t)(v >> 32)); }
+
+// zlib's crc32 on the host (header and index only: 8 bytes per block); crc = 0 starts, a result continues
+uint32_t host_crc32(uint32_t crc, const uint8_t* p, uint64_t n) {
+    static const std::vector<uint32_t> table = [] {
+        std::vector<uint32_t> t(256);
+        for (uint32_t i = 0; i < 256; i++) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; k++) { c = (c >> 1) ^ ((0u - (c & 1u)) & 0xEDB88320u); }
+            t[i] = c;
+        }
+        return t;
+    }();
+    crc = ~crc;
+    for (uint64_t k = 0; k < n; k++) { crc = table[(crc ^ p[k]) & 0xFFu] ^ (crc >> 8); }
+    return ~crc;
+}
+
+bool frame_params_ok(uint32_t win_bits, uint32_t block_bits) {
+    return win_bits >= (uint32_t)sqz_min_win_bits && win_bits <= (uint32_t)sqz_max_win_bits &&
+           block_bits >= (uint32_t)sqz_frame_min_block_bits && block_bits <= (uint32_t)sqz_frame_max_block_bits;
+}
+uint64_t frame_blocks(uint64_t content_bytes, uint32_t block_bits) {
+    return (content_bytes >> block_bits) + ((content_bytes & ((1ull << block_bits) - 1)) != 0 ? 1 : 0);
+}
+uint64_t frame_payload_off(uint64_t n_blocks) { return align_up(32 + 8 * n_blocks, 16); }
+
+// content bytes a host call works through per pass (whole blocks, one at least)
+uint64_t frame_pass_blocks(uint64_t block_bytes) {
+    uint64_t pass = 1ull << 30;
+    const char* e = getenv("SQZ_FRAME_PASS_BYTES");         // read at every call: a test sets it low
+    if (e != NULL && atoll(e) > 0) { pass = (uint64_t)atoll(e); }
+    const uint64_t blocks = pass / block_bytes;
+    return blocks < 1 ? 1 : (blocks > 0x7FFFFFFFull ? 0x7FFFFFFFull : blocks);
+}
+
+// where the pieces of a device call's scratch lie (every piece 256-byte aligned)
+struct FrameScratch {
+    uint64_t in_off, out_off, out_bytes, copy_bytes, dense_off, crc, misc, slabs, codec, codec_bytes, total;
+};
+FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_bytes, bool encode) {
+    FrameScratch L = {};
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) { const uint64_t r = at; at += align_up(bytes, 256); return r; };
+    L.in_off = take((n + 1) * 8);
+    L.out_off = take((n + 1) * 8);                          // encode: the slabs' offsets
+    L.crc = take(n * 4 + 4);
+    L.misc = take(256);                                     // [0,16) the index's range, [16,20) its checksum, [32,48) spare
+    if (encode) {
+        L.out_bytes = take(n * 8);
+        L.copy_bytes = take(n * 8);
+        L.dense_off = take((n + 1) * 8);
+        L.slabs = take(n * slab_bytes);
+        L.codec_bytes = sqz_hip_encode_scratch_bytes((uint32_t)n, content_bytes);
+    } else {
+        L.codec_bytes = sqz_hip_decode_scratch_bytes((uint32_t)n, content_bytes);
+    }
+    L.codec = take(L.codec_bytes);
+    L.total = at;
+    return L;
+}
+
+// the device side of a frame encode: everything enqueued on st, nothing waits
+int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
+                     uint8_t* d_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
+                     int32_t* d_err, uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st) {
+    const uint64_t bb = 1ull << block_bits, n64 = frame_blocks(content_bytes, block_bits);
+    if (n64 > 0xFFFFFFFFull) { return EINVAL; }
+    const uint32_t n = (uint32_t)n64;
+    const uint64_t slab = sqz_bound(bb);
+    const FrameScratch L = frame_scratch(n, content_bytes, slab, true);
+    if (scratch_bytes < L.total) { return EINVAL; }
+    uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
+    uint64_t* slab_off = (uint64_t*)(scratch + L.out_off);
+    uint64_t* out_bytes = (uint64_t*)(scratch + L.out_bytes);
+    uint64_t* copy_bytes = (uint64_t*)(scratch + L.copy_bytes);
+    uint64_t* dense_off = (uint64_t*)(scratch + L.dense_off);
+    uint32_t* crc = (uint32_t*)(scratch + L.crc);
+    uint64_t* idx_off = (uint64_t*)(scratch + L.misc);
+    uint32_t* idx_crc = (uint32_t*)(scratch + L.misc + 16);
+    sqzk::launch_frame_plan(n, bb, content_bytes, slab, in_off, slab_off, st);
+    if (n > 0) {
+        { SpanGuard g(st, SQZ_HIP_K_CRC32);
+          sqzk::launch_crc32_blocks(d_in, in_off, n, crc, bb, st); }
+        const uint64_t head = align_up((uint64_t)n * 4, 256);
+        const uint64_t slots = (L.codec_bytes - head) / 8;
+        uint32_t* counts = (uint32_t*)(scratch + L.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + L.codec + head);
+        run_encode(finder_default(), d_in, in_off, n, 1u << win_bits, tokens, counts, tokens, tokens + slots, bb,
+                   scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st);
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frame_index(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, d_frame, capacity,
+                               copy_bytes, dense_off, idx_off, d_frame_bytes, d_status, st); }
+    { SpanGuard g(st, SQZ_HIP_K_CRC32);
+      sqzk::launch_crc32_blocks(d_frame, idx_off, 1, idx_crc, 8 * (uint64_t)n, st); }
+    sqzk::launch_frame_seal(d_frame, idx_crc, n, d_status, st);
+    if (n > 0) {
+        sqzk::launch_compact_blocks(scratch + L.slabs, slab_off, copy_bytes, n, d_frame, dense_off, bb / 2, st);
+    }
+    return hip_errno(hipGetLastError());
+}
+
+// the device side of a frame decode, blocks [first, first + n_sel) into d_out (block `first` at its start)
+int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_t content_bytes, uint32_t first,
+                     uint32_t n_sel, uint64_t sel_bytes, uint8_t* d_out, int32_t* d_err, int32_t* d_status,
+                     uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st) {
+    const FrameScratch L = frame_scratch(n_sel, sel_bytes, 0, false);
+    if (scratch_bytes < L.total || avail < 32 + 8 * (uint64_t)n) { return scratch_bytes < L.total ? EINVAL : E2BIG; }
+    uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
+    uint64_t* out_off = (uint64_t*)(scratch + L.out_off);
+    uint32_t* crc = (uint32_t*)(scratch + L.crc);
+    uint64_t* idx_off = (uint64_t*)(scratch + L.misc);
+    uint32_t* idx_crc = (uint32_t*)(scratch + L.misc + 16);
+    uint64_t* spare = (uint64_t*)(scratch + L.misc + 32);
+    // {0, 8 n}: the index as one range behind the header, written on the device (no host copy to wait for)
+    sqzk::launch_frame_plan(1, 8 * (uint64_t)n, 8 * (uint64_t)n, 0, idx_off, spare, st);
+    { SpanGuard g(st, SQZ_HIP_K_CRC32);
+      sqzk::launch_crc32_blocks(d_frame + 32, idx_off, 1, idx_crc, 8 * (uint64_t)n, st); }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frame_open(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, in_off, out_off, d_status, st); }
+    if (n_sel > 0) {
+        uint32_t* counts = (uint32_t*)(scratch + L.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + L.codec + align_up((uint64_t)n_sel * 4, 256));
+        { SpanGuard g(st, SQZ_HIP_K_ENTROPY_DECODE);
+          sqzk::launch_entropy_decode(d_frame, in_off, out_off, tokens, counts, d_err, nullptr, n_sel, 0,
+                                      decode_waves_for(n_sel), st); }
+        { SpanGuard g(st, SQZ_HIP_K_LZ_EXPAND);
+          sqzk::launch_lz_expand(tokens, counts, d_out, out_off, n_sel, st); }
+        { SpanGuard g(st, SQZ_HIP_K_CRC32);
+          sqzk::launch_crc32_blocks(d_out, out_off, n_sel, crc, (sel_bytes + n_sel - 1) / n_sel, st); }
+        sqzk::launch_frame_verify(d_frame, first, n_sel, crc, d_status, d_err, st);
+    }
+    return hip_errno(hipGetLastError());
+}
+
+// host flavour of decode: blocks [b_first, b_end) of a frame that sqz_frame_info has checked WITH its index, in
+// passes; sink(first block of the pass, blocks, their errnos, device pointer to their bytes, how many) takes what
+// it wants of each pass with copies on st and returns an errno.  The device holds an image of the whole frame, of
+// which only header, index and the streams of the blocks asked for are uploaded.
+template <class Sink>
+int frame_decode_host(Lane& c, hipStream_t st, const uint8_t* frame, const struct sqz_frame_info& fi,
+                      uint64_t b_first, uint64_t b_end, Sink sink) {
+    const uint64_t bb = fi.block_bytes, n = fi.n_blocks;
+    std::vector<uint64_t> pre(n + 1);
+    pre[0] = 0;
+    for (uint64_t b = 0; b < n; b++) { pre[b + 1] = pre[b] + 8 * (uint64_t)get_le32(frame + 32 + 8 * b); }
+    int e;
+    if ((e = c.dense.reserve(fi.frame_bytes + 16)) || (e = c.misc.reserve(256))) { return e; }
+    uint8_t* const d_frame = (uint8_t*)c.dense.p;
+    HIP_TRY(hipMemcpyAsync(d_frame, frame, fi.payload_off, hipMemcpyHostToDevice, st));
+    const uint64_t pass = frame_pass_blocks(bb);
+    std::vector<int32_t> errs;
+    for (uint64_t p0 = b_first; p0 < b_end; p0 += pass) {
+        const uint64_t pn = b_end - p0 < pass ? b_end - p0 : pass;
+        const uint64_t c0 = p0 * bb, c1 = (p0 + pn) * bb < fi.content_bytes ? (p0 + pn) * bb : fi.content_bytes;
+        const FrameScratch L = frame_scratch(pn, c1 - c0, 0, false);
+        if ((e = c.out.reserve(c1 - c0 + 16)) || (e = c.work_a.reserve(L.total)) || (e = c.err.reserve(pn * 4))) { return e; }
+        if (pre[p0 + pn] > pre[p0]) {
+            HIP_TRY(hipMemcpyAsync(d_frame + fi.payload_off + pre[p0], frame + fi.payload_off + pre[p0],
+                                   pre[p0 + pn] - pre[p0], hipMemcpyHostToDevice, st));
+        }
+        if ((e = frame_decode_dev(d_frame, fi.frame_bytes, (uint32_t)n, fi.content_bytes, (uint32_t)p0, (uint32_t)pn,
+                                  c1 - c0, (uint8_t*)c.out.p, (int32_t*)c.err.p, (int32_t*)c.misc.p,
+                                  (uint8_t*)c.work_a.p, L.total, st)) != 0) { return e; }
+        errs.resize(pn);
+        int32_t status = 0;
+        HIP_TRY(hipMemcpyAsync(errs.data(), c.err.p, pn * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&status, c.misc.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (status != 0) { return status; }
+        if ((e = sink(p0, pn, errs.data(), (const uint8_t*)c.out.p, c1 - c0)) != 0) { return e; }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+// a frame whose header, index AND extent the host has checked: what every host decode call starts with
+int frame_check_host(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* fi) {
+    const int e = sqz_frame_info(frame, avail, fi);
+    if (e != 0) { return e; }
+    return avail < fi->payload_off ? E2BIG : 0;             // the index was not covered, so not checked
 }
 
 } // namespace
@@ -1001,6 +1199,217 @@ uint64_t sqz_rc_decompress(struct sqz_rc* s, void* data, size_t bytes) {        
         s->rc.error = err;
         return produced < bytes ? produced : bytes;
     }
+}
+
+// ------------------------------------------------------------------ SQZF frames
+uint64_t sqz_frame_bound(uint64_t content_bytes, uint32_t block_bits) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits) { return 0; }
+    const uint64_t bb = 1ull << block_bits, full = content_bytes >> block_bits, tail = content_bytes & (bb - 1);
+    return frame_payload_off(full + (tail != 0 ? 1 : 0)) + full * sqz_bound(bb) + (tail != 0 ? sqz_bound(tail) : 0);
+}
+
+int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* out) {
+    if (frame == NULL || out == NULL) { return EINVAL; }
+    if (avail < 32) { return E2BIG; }
+    const uint32_t win_bits = frame[5], block_bits = frame[6];
+    if (get_le32(frame) != 0x465A5153u || frame[4] != 1 || frame[7] != 0 || !frame_params_ok(win_bits, block_bits)) {
+        return EINVAL;
+    }
+    const uint64_t content = get_le64(frame + 8), payload = get_le64(frame + 16);
+    const uint64_t n = get_le32(frame + 24);
+    if (frame_blocks(content, block_bits) != n || (payload & 7u) != 0) { return EINVAL; }
+    const uint64_t payload_off = frame_payload_off(n);      // n < 2^32: no overflow
+    if (payload > ~(uint64_t)0 - payload_off) { return EINVAL; }
+    out->content_bytes = content;
+    out->payload_bytes = payload;
+    out->payload_off = payload_off;
+    out->frame_bytes = payload_off + payload;
+    out->block_bytes = 1ull << block_bits;
+    out->n_blocks = (uint32_t)n;
+    out->win_bits = win_bits;
+    out->version = frame[4];
+    out->reserved = 0;
+    if (avail >= 32 + 8 * n) {                              // the index is there: check it too
+        const uint32_t crc = host_crc32(host_crc32(0, frame, 28), frame + 32, 8 * n);
+        if (crc != get_le32(frame + 28)) { return EILSEQ; }
+        uint64_t words = 0;
+        for (uint64_t b = 0; b < n; b++) { words += get_le32(frame + 32 + 8 * b); }    // < 2^64: n, words < 2^32
+        if (words != payload / 8) { return EINVAL; }
+    }
+    return 0;
+}
+
+int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                       uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
+    if (frame_bytes == NULL || (frame == NULL && capacity > 0) || (data == NULL && bytes > 0) ||
+        !frame_params_ok(win_bits, block_bits)) { return EINVAL; }
+    const uint64_t bb = 1ull << block_bits, n = frame_blocks(bytes, block_bits);
+    if (n > 0xFFFFFFFFull) { return EINVAL; }
+    const uint64_t payload_off = frame_payload_off(n), slab = sqz_bound(bb);
+    bool fits = capacity >= payload_off;
+    std::vector<uint8_t> head(payload_off, 0);              // header, index, padding: built here, copied at the end
+    uint64_t payload = 0;
+    if (n > 0) {
+        int e = device_ready();
+        if (e != 0) { return e; }
+        LaneLease lease;
+        Lane& c = *lease.lane;
+        hipStream_t st = lease.stream(nullptr);
+        const uint64_t pass = frame_pass_blocks(bb);
+        std::vector<uint64_t> out_bytes, dense_off;
+        std::vector<int32_t> err;
+        std::vector<uint32_t> crc;
+        for (uint64_t p0 = 0; p0 < n; p0 += pass) {
+            const uint32_t pn = (uint32_t)(n - p0 < pass ? n - p0 : pass);
+            const uint64_t c0 = p0 * bb, c1 = (p0 + pn) * bb < bytes ? (p0 + pn) * bb : bytes, total_in = c1 - c0;
+            if ((e = c.in.reserve(total_in + 16)) || (e = c.out.reserve((uint64_t)pn * slab + 16)) ||
+                (e = c.in_off.reserve(((uint64_t)pn + 1) * 8)) || (e = c.out_off.reserve(((uint64_t)pn + 1) * 8)) ||
+                (e = c.tok_count.reserve((size_t)pn * 4)) || (e = c.crc.reserve((size_t)pn * 4)) ||
+                (e = c.work_a.reserve((total_in + 64) * 4)) || (e = c.work_m.reserve((total_in + 64) * 4)) ||
+                (e = c.out_bytes.reserve((size_t)pn * 8)) || (e = c.err.reserve((size_t)pn * 4))) { return e; }
+            HIP_TRY(hipMemcpyAsync(c.in.p, data + c0, total_in, hipMemcpyHostToDevice, st));
+            sqzk::launch_frame_plan(pn, bb, total_in, slab, (uint64_t*)c.in_off.p, (uint64_t*)c.out_off.p, st);
+            { SpanGuard g(st, SQZ_HIP_K_CRC32);
+              sqzk::launch_crc32_blocks((const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, (uint32_t*)c.crc.p, bb, st); }
+            run_encode(finder_default(), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, 1u << win_bits,
+                       (uint32_t*)c.work_a.p, (uint32_t*)c.tok_count.p, (uint32_t*)c.work_a.p, (uint32_t*)c.work_m.p, bb,
+                       (uint8_t*)c.out.p, (const uint64_t*)c.out_off.p, (uint64_t*)c.out_bytes.p, (int32_t*)c.err.p,
+                       0, 0, total_in + 64, nullptr, st);
+            HIP_TRY(hipGetLastError());
+            out_bytes.resize(pn); err.resize(pn); crc.resize(pn); dense_off.resize((size_t)pn + 1);
+            HIP_TRY(hipMemcpyAsync(out_bytes.data(), c.out_bytes.p, (size_t)pn * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(err.data(), c.err.p, (size_t)pn * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(crc.data(), c.crc.p, (size_t)pn * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            dense_off[0] = 0;
+            for (uint32_t b = 0; b < pn; b++) {
+                if (err[b] != 0) { return err[b]; }
+                if ((out_bytes[b] & 7u) != 0 || out_bytes[b] / 8 > 0xFFFFFFFFull) { return EINVAL; }
+                dense_off[b + 1] = dense_off[b] + out_bytes[b];
+                put_le32(head.data() + 32 + 8 * (p0 + b), (uint32_t)(out_bytes[b] / 8));
+                put_le32(head.data() + 32 + 8 * (p0 + b) + 4, crc[b]);
+            }
+            const uint64_t dense_total = dense_off[pn];
+            fits = fits && dense_total <= capacity - payload_off - payload;
+            if (fits && dense_total > 0) {                  // the pass's streams leave as one transfer to their place
+                if ((e = c.dense.reserve(dense_total + 16)) || (e = c.dense_off.reserve(((size_t)pn + 1) * 8))) { return e; }
+                HIP_TRY(hipMemcpyAsync(c.dense_off.p, dense_off.data(), ((size_t)pn + 1) * 8, hipMemcpyHostToDevice, st));
+                sqzk::launch_compact_blocks((const uint8_t*)c.out.p, (const uint64_t*)c.out_off.p,
+                                            (const uint64_t*)c.out_bytes.p, pn, (uint8_t*)c.dense.p,
+                                            (const uint64_t*)c.dense_off.p, dense_total / pn, st);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(frame + payload_off + payload, c.dense.p, dense_total, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+            payload += dense_total;
+        }
+    }
+    *frame_bytes = payload_off + payload;
+    if (!fits) { return E2BIG; }
+    uint8_t* h = head.data();
+    put_le32(h, 0x465A5153u);
+    h[4] = 1; h[5] = (uint8_t)win_bits; h[6] = (uint8_t)block_bits; h[7] = 0;
+    put_le64(h + 8, bytes);
+    put_le64(h + 16, payload);
+    put_le32(h + 24, (uint32_t)n);
+    put_le32(h + 28, host_crc32(host_crc32(0, h, 28), h + 32, 8 * n));
+    memcpy(frame, h, payload_off);
+    return 0;
+}
+
+int sqz_frame_decompress(const uint8_t* frame, uint64_t avail, uint8_t* data, uint64_t capacity,
+                         uint64_t* bytes, int32_t* block_err) {
+    struct sqz_frame_info fi;
+    int e = frame_check_host(frame, avail, &fi);
+    if (e != 0) { return e; }
+    if (bytes != NULL) { *bytes = fi.content_bytes; }
+    if (avail < fi.frame_bytes || capacity < fi.content_bytes) { return E2BIG; }
+    if (fi.n_blocks == 0) { return 0; }
+    if (data == NULL) { return EINVAL; }
+    if ((e = device_ready()) != 0) { return e; }
+    LaneLease lease;
+    hipStream_t st = lease.stream(nullptr);
+    int first_bad = 0;
+    e = frame_decode_host(*lease.lane, st, frame, fi, 0, fi.n_blocks,
+        [&](uint64_t p0, uint64_t pn, const int32_t* errs, const uint8_t* d_bytes, uint64_t count) -> int {
+            for (uint64_t k = 0; k < pn; k++) {
+                if (block_err != NULL) { block_err[p0 + k] = errs[k]; }
+                if (first_bad == 0) { first_bad = errs[k]; }
+            }
+            if (count > 0) {
+                HIP_TRY(hipMemcpyAsync(data + p0 * fi.block_bytes, d_bytes, count, hipMemcpyDeviceToHost, st));
+            }
+            return 0;
+        });
+    return e != 0 ? e : first_bad;
+}
+
+int sqz_frame_read(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length, uint8_t* out) {
+    struct sqz_frame_info fi;
+    int e = frame_check_host(frame, avail, &fi);
+    if (e != 0) { return e; }
+    if (offset > fi.content_bytes || length > fi.content_bytes - offset || (out == NULL && length > 0)) { return EINVAL; }
+    if (length == 0) { return 0; }
+    const uint64_t bb = fi.block_bytes, b_first = offset / bb, b_end = (offset + length - 1) / bb + 1;
+    uint64_t words = 0;                                     // the covering streams must be inside avail
+    for (uint64_t b = 0; b < b_end; b++) { words += get_le32(frame + 32 + 8 * b); }
+    if (8 * words > avail - fi.payload_off) { return E2BIG; }
+    if ((e = device_ready()) != 0) { return e; }
+    LaneLease lease;
+    hipStream_t st = lease.stream(nullptr);
+    return frame_decode_host(*lease.lane, st, frame, fi, b_first, b_end,
+        [&](uint64_t p0, uint64_t pn, const int32_t* errs, const uint8_t* d_bytes, uint64_t count) -> int {
+            for (uint64_t k = 0; k < pn; k++) { if (errs[k] != 0) { return errs[k]; } }
+            const uint64_t lo = offset > p0 * bb ? offset : p0 * bb;
+            const uint64_t hi = offset + length < p0 * bb + count ? offset + length : p0 * bb + count;
+            if (hi > lo) {
+                HIP_TRY(hipMemcpyAsync(out + (lo - offset), d_bytes + (lo - p0 * bb), hi - lo, hipMemcpyDeviceToHost, st));
+            }
+            return 0;
+        });
+}
+
+uint64_t sqz_hip_frame_scratch_bytes(uint64_t content_bytes, uint32_t block_bits, int encode) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits) { return 0; }
+    const uint64_t n = frame_blocks(content_bytes, block_bits);
+    return frame_scratch(n, content_bytes, sqz_bound(1ull << block_bits), encode != 0).total;
+}
+
+int sqz_hip_frame_encode(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
+                         void* d_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
+                         int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!frame_params_ok(win_bits, block_bits) || (d_in == NULL && content_bytes > 0) || d_frame == NULL ||
+        ((uintptr_t)d_frame & 15u) != 0 || d_frame_bytes == NULL || d_status == NULL ||
+        (d_err == NULL && content_bytes > 0) || d_scratch == NULL || ((uintptr_t)d_scratch & 15u) != 0) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    return frame_encode_dev((const uint8_t*)d_in, content_bytes, win_bits, block_bits, (uint8_t*)d_frame, capacity,
+                            d_frame_bytes, d_status, d_err, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int sqz_hip_frame_decode(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                         void* d_out, int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                         void* stream) {
+    if (d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 || d_status == NULL || d_scratch == NULL ||
+        ((uintptr_t)d_scratch & 15u) != 0 || (n_blocks > 0 && (d_out == NULL || d_err == NULL)) ||
+        (n_blocks == 0) != (content_bytes == 0) || content_bytes / (1ull << sqz_frame_min_block_bits) + 1 < n_blocks) {
+        return EINVAL;
+    }
+    if (avail < 32 + 8 * (uint64_t)n_blocks) { return E2BIG; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    return frame_decode_dev((const uint8_t*)d_frame, avail, n_blocks, content_bytes, 0, n_blocks, content_bytes,
+                            (uint8_t*)d_out, d_err, d_status, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t* d_crc, void* stream) {
+    if (n == 0) { return 0; }
+    if (d_in == NULL || d_in_off == NULL || d_crc == NULL) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    SpanGuard g((hipStream_t)stream, SQZ_HIP_K_CRC32);
+    sqzk::launch_crc32_blocks((const uint8_t*)d_in, d_in_off, n, d_crc, 0, (hipStream_t)stream);
+    return hip_errno(hipGetLastError());
 }
 
 // ------------------------------------------------------------------ timing

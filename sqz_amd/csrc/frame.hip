@@ -1,0 +1,455 @@
+// sqz_amd/csrc/frame.hip -- the SQZF frame container on the device (gfx950): content checksums,
+// index construction (encode) and index validation (decode).  Format: include/sqz/sqz.h, DESIGN.md section 10.
+//
+// CRC-32 as zlib.crc32 computes it (IEEE 802.3, reflected polynomial 0xEDB88320, initial value and final
+// xor 0xFFFFFFFF).  CRC is serial in its textbook form; here it is split by linearity.  With r(M) the
+// register after feeding M from state 0 without the final xor,
+//     r(A || B) = r(A) * x^(8|B|)  ^  r(B)                 (products of reflected residues mod P)
+//     crc(M)    = r(M) ^ 0xFFFFFFFF * x^(8|M|) ^ 0xFFFFFFFF
+// and zero bytes IN FRONT of a message leave r unchanged.  crc32_blocks_kernel cuts a byte range into
+// 64-byte chunks on 16-byte ADDRESS boundaries (so every full row is one aligned 16-byte load; the
+// bytes of the first row that lie before the range count as zeros, which is free), lane t of a
+// 256-lane workgroup reduces chunks t, t + 256, ... and carries them forward with the compile-time
+// multiplier x^(8 * 16384), the lanes are brought to a common end with a 256-entry table of x^(512 d),
+// xor-reduced, and the ragged last chunk (1..64 bytes, reduced byte-exactly by the lane that owns it)
+// is appended.  A long range is shared by several workgroups: each adds its part, moved to the end of
+// the range by x^(8 * bytes behind it), with an atomic xor.
+//
+// The per-chunk reduction is the table-free bitwise loop: three vector operations per message bit on gfx950
+// (v_bfe_i32, v_lshrrev_b32, v_bitop3_b32), no LDS and no table traffic, so the kernel is bound by
+// instruction issue, not by HBM.  Slicing tables in LDS would trade those for one 4-byte LDS read per byte
+// at data-dependent addresses; they were not built: DESIGN.md section 10 has the measured time of this form
+// against the encode step it rides on.
+#include "sqz_kernels.h"
+
+namespace sqzk {
+
+namespace {
+
+constexpr uint32_t kCrcPoly = 0xEDB88320u;
+constexpr uint32_t kCrcOne = 0x80000000u;          // x^0 in the reflected representation
+constexpr int kCrcThreads = 256;
+constexpr uint32_t kChunk = 64;                    // bytes a lane reduces at a time: four 16-byte rows
+constexpr uint64_t kMinPart = 16384;               // a workgroup's share of a range: at least one tile
+
+constexpr int kErrEINVAL = 22, kErrE2BIG = 7, kErrEILSEQ = 84;     // <errno.h>, checked in abi.hip
+
+// a * b mod P, both reflected residues: 32 shift-and-xor steps (constexpr: host, device and tables)
+constexpr uint32_t gf_mul(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 0; i < 32; i++) {
+        p ^= (0u - ((a >> (31 - i)) & 1u)) & b;
+        b = (b >> 1) ^ ((0u - (b & 1u)) & kCrcPoly);
+    }
+    return p;
+}
+
+struct CrcTables {
+    uint32_t pow2[32];     // x^(2^k); x^(2^32 - 1) = 1, so x^(2^(k + 32)) = x^(2^k)
+    uint32_t m512[256];    // x^(512 d): the bits of d chunks
+};
+constexpr CrcTables make_crc_tables() {
+    CrcTables t{};
+    uint32_t p = kCrcOne >> 1;                     // x^1
+    t.pow2[0] = p;
+    for (int k = 1; k < 32; k++) { p = gf_mul(p, p); t.pow2[k] = p; }
+    uint32_t m = kCrcOne;
+    for (int d = 0; d < 256; d++) { t.m512[d] = m; m = gf_mul(m, t.pow2[9]); }
+    return t;
+}
+constexpr CrcTables kCrcTablesValue = make_crc_tables();
+constexpr uint32_t kTileMul = kCrcTablesValue.pow2[17];            // x^(8 * 256 * 64): one tile of chunks further
+__device__ const CrcTables kCrcTab = kCrcTablesValue;
+
+// a * K for a compile-time K: after unrolling every K * x^i is a constant, three operations per bit of a
+template <uint32_t K>
+__device__ __forceinline__ uint32_t gf_mul_const(uint32_t a) {
+    uint32_t p = 0, b = K;
+#pragma unroll
+    for (int i = 0; i < 32; i++) {
+        p ^= (0u - ((a >> (31 - i)) & 1u)) & b;
+        b = (b >> 1) ^ ((0u - (b & 1u)) & kCrcPoly);
+    }
+    return p;
+}
+
+// the register after `bits` more message bits whose values were xored into its low end already
+__device__ __forceinline__ uint32_t crc_shift(uint32_t c, int bits) {
+    for (int k = 0; k < bits; k++) { c = (c >> 1) ^ ((0u - (c & 1u)) & kCrcPoly); }
+    return c;
+}
+__device__ __forceinline__ uint32_t crc_word(uint32_t c) {         // four message bytes (little-endian word)
+#pragma unroll
+    for (int k = 0; k < 32; k++) { c = (c >> 1) ^ ((0u - (c & 1u)) & kCrcPoly); }
+    return c;
+}
+
+// x^(8 n) by the whole wave: lane j holds x^(8 * 2^j) where bit j of n is set, the product goes round in a
+// butterfly (six multiplications).  Every lane of the wave must call it; every lane gets the result.
+__device__ __forceinline__ uint32_t xpow8_wave(uint64_t n, int lane) {
+    uint32_t f = ((n >> (lane & 63)) & 1ull) != 0 ? kCrcTab.pow2[(lane + 3) & 31] : kCrcOne;
+    if (lane >= 61) { f = kCrcOne; }
+    for (int o = 1; o < 64; o <<= 1) { f = gf_mul(f, (uint32_t)__shfl_xor((int)f, o)); }
+    return f;
+}
+
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+    for (int o = 1; o < 64; o <<= 1) { v ^= (uint32_t)__shfl_xor((int)v, o); }
+    return v;
+}
+
+// bytes [lo, hi) of the 16-byte row at p (16-byte aligned), the others zero: one aligned load for a whole
+// row, single bytes otherwise -- nothing outside the range is read
+__device__ __forceinline__ uint4 load_row_bytes(const uint8_t* p, uint32_t lo, uint32_t hi) {
+    if (lo == 0 && hi >= 16) { return *reinterpret_cast<const uint4*>(p); }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t k = lo; k < hi && k < 16; k++) { w[k >> 2] |= (uint32_t)p[k] << (8 * (k & 3)); }
+    uint4 r;
+    r.x = w[0]; r.y = w[1]; r.z = w[2]; r.w = w[3];
+    return r;
+}
+
+// zlib crc32 of a few bytes on one lane (the 28 header bytes of a frame)
+__device__ __forceinline__ uint32_t crc32_small(const uint8_t* p, uint32_t n) {
+    uint32_t c = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < n; k++) { c = crc_shift(c ^ p[k], 8); }
+    return c ^ 0xFFFFFFFFu;
+}
+
+__device__ __forceinline__ uint32_t load_le32(const uint8_t* p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+__device__ __forceinline__ uint64_t load_le64(const uint8_t* p) {
+    return (uint64_t)load_le32(p) | ((uint64_t)load_le32(p + 4) << 32);
+}
+
+} // namespace
+
+// crc[b] = zlib.crc32(in[off[b] .. off[b + 1])).  `groups` workgroups share a range (parts of equal size, a
+// multiple of 4096, at least kMinPart); with groups > 1 crc[] must be zero at the start: the parts are
+// xored in.
+__global__ __launch_bounds__(kCrcThreads)
+void crc32_blocks_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ off, uint32_t n_ranges,
+                         uint32_t* __restrict__ crc, uint32_t groups) {
+    __shared__ uint32_t red[2][kCrcThreads / 64];
+    const uint32_t b = blockIdx.x / groups, g = blockIdx.x % groups;
+    if (b >= n_ranges) { return; }
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t o0 = off[b], o1 = off[b + 1];
+    const uint64_t len = o1 > o0 ? o1 - o0 : 0;
+    uint64_t part = (len + groups - 1) / groups;
+    part = (part + 4095) & ~(uint64_t)4095;
+    if (part < kMinPart) { part = kMinPart; }
+    const uint64_t s = (uint64_t)g * part < len ? (uint64_t)g * part : len;
+    const uint64_t e = len - s > part ? s + part : len;
+    if (g != 0 && s >= e) { return; }              // nothing here (the whole workgroup leaves); part 0 stays for the
+                                                   // initial value and final xor, also of an empty range
+    const uint8_t* const p0 = in + o0 + s;
+    const uint64_t plen = e - s;
+    const uint32_t head = (uint32_t)((uintptr_t)p0 & 15u);
+    const uint8_t* const pa = p0 - head;           // 16-byte aligned; the `head` bytes before p0 count as zeros
+    const uint64_t span = plen > 0 ? head + plen : 0;
+    const uint64_t nch = (span + kChunk - 1) / kChunk;
+    const uint64_t m = nch > 0 ? nch - 1 : 0;      // chunks that end on a chunk boundary; chunk m is the last one
+    const uint32_t last_len = (uint32_t)(span - m * kChunk);   // 1..64 (0 for an empty part)
+
+    uint32_t acc = 0, c_last = 0;
+    uint64_t jl = 0;
+    bool have = false;
+    for (uint64_t j = (uint64_t)tid; j < nch; j += kCrcThreads) {
+        const uint8_t* const row = pa + j * kChunk;
+        const uint32_t lo = j == 0 ? head : 0u;                // first valid byte of the chunk
+        const uint32_t hi = j == m ? last_len : kChunk;        // one past its last valid byte
+        uint4 r[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint32_t a = lo > 16 * k ? lo - 16 * k : 0u;
+            const uint32_t z = hi > 16 * k ? hi - 16 * k : 0u;
+            if (z > a) { r[k] = load_row_bytes(row + 16 * k, a, z); } else { r[k].x = r[k].y = r[k].z = r[k].w = 0u; }
+        }
+        const uint32_t w[16] = {r[0].x, r[0].y, r[0].z, r[0].w, r[1].x, r[1].y, r[1].z, r[1].w,
+                                r[2].x, r[2].y, r[2].z, r[2].w, r[3].x, r[3].y, r[3].z, r[3].w};
+        uint32_t c = 0;
+        if (j < m) {
+#pragma unroll
+            for (int i = 0; i < 16; i++) { c = crc_word(c ^ w[i]); }
+            acc = gf_mul_const<kTileMul>(acc) ^ c;
+            jl = j;
+            have = true;
+        } else {                                   // the last chunk: exactly `hi` bytes (those before `lo` are zeros)
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int nb = (int)hi - 4 * i;
+                if (nb >= 4) { c = crc_word(c ^ w[i]); }
+                else if (nb > 0) { c = crc_shift(c ^ w[i], 8 * nb); }
+            }
+            c_last = c;
+        }
+    }
+    // every lane's chunks to the end of chunk m - 1, then one value per workgroup
+    uint32_t mine = have ? gf_mul(acc, kCrcTab.m512[(m - 1 - jl) & 255u]) : 0u;
+    mine = wave_xor(mine);
+    c_last = wave_xor(c_last);
+    if (lane == 0) { red[0][wave] = mine; red[1][wave] = c_last; }
+    __syncthreads();
+    if (wave != 0) { return; }
+    uint32_t sum = 0, tail = 0;
+    for (int k = 0; k < kCrcThreads / 64; k++) { sum ^= red[0][k]; tail ^= red[1][k]; }
+    uint32_t r = nch > 0 ? gf_mul(sum, xpow8_wave(last_len, lane)) ^ tail : 0u;
+    const uint64_t behind = len - e;               // bytes of the range behind this part
+    if (behind > 0) { r = gf_mul(r, xpow8_wave(behind, lane)); }
+    if (g == 0) { r ^= gf_mul(0xFFFFFFFFu, xpow8_wave(len, lane)) ^ 0xFFFFFFFFu; }
+    if (lane == 0) {
+        if (groups == 1) { crc[b] = r; } else { atomicXor(&crc[b], r); }
+    }
+}
+
+void launch_crc32_blocks(const uint8_t* in, const uint64_t* off, uint32_t n_ranges, uint32_t* crc,
+                         uint64_t size_hint, hipStream_t stream) {
+    if (n_ranges == 0) { return; }
+    // one workgroup per 64 KB of a range when the batch alone does not fill the chip (about 4096 workgroups
+    // do); a range whose size the host does not know gets the most, and the surplus leaves at once
+    uint64_t groups = size_hint != 0 ? (size_hint + 65535) / 65536 : 1024;
+    const uint64_t cap = 4096 / n_ranges > 1 ? 4096 / n_ranges : 1;
+    if (groups > cap) { groups = cap; }
+    if (groups > 1024) { groups = 1024; }
+    if (groups < 1) { groups = 1; }
+    while (groups > 1 && groups * n_ranges > 0x7FFFFFFFull) { groups /= 2; }
+    if (groups > 1) {
+#ifdef SQZ_WAVE_EMU
+        memset(crc, 0, (size_t)n_ranges * 4);
+#else
+        (void)hipMemsetAsync(crc, 0, (size_t)n_ranges * 4, stream);
+#endif
+    }
+    hipLaunchKernelGGL(crc32_blocks_kernel, dim3((unsigned)(groups * n_ranges)), dim3(kCrcThreads), 0, stream,
+                       in, off, n_ranges, crc, (uint32_t)groups);
+}
+
+// ---------------------------------------------------------------------------------------- encode side
+// the uniform cut of a buffer into blocks and of the slab area into slabs, on the device (no host copy)
+__global__ __launch_bounds__(256)
+void frame_plan_kernel(uint32_t n_blocks, uint64_t block_bytes, uint64_t content_bytes, uint64_t slab_bytes,
+                       uint64_t* __restrict__ in_off, uint64_t* __restrict__ slab_off) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > n_blocks) { return; }
+    const uint64_t at = k * block_bytes;
+    in_off[k] = at < content_bytes ? at : content_bytes;
+    slab_off[k] = k * slab_bytes;
+}
+
+void launch_frame_plan(uint32_t n_blocks, uint64_t block_bytes, uint64_t content_bytes, uint64_t slab_bytes,
+                       uint64_t* in_off, uint64_t* slab_off, hipStream_t stream) {
+    const uint64_t grid = ((uint64_t)n_blocks + 1 + 255) / 256;
+    hipLaunchKernelGGL(frame_plan_kernel, dim3((unsigned)grid), dim3(256), 0, stream,
+                       n_blocks, block_bytes, content_bytes, slab_bytes, in_off, slab_off);
+}
+
+// One workgroup: exclusive scan of the stream sizes, then header, index, padding, the dense offsets for
+// compact_blocks_kernel (absolute, from the start of the frame), frame_bytes and the status.  A frame that
+// does not fit `capacity`, or a block the encoder failed, leaves the frame untouched: copy_bytes[] = 0 makes
+// the compaction a no-op, idx_off = {0, 0} the index checksum an empty range.  The index_crc field is
+// written by frame_seal_kernel once the index has been summed.
+__global__ __launch_bounds__(256)
+void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
+                        const uint32_t* __restrict__ crc, uint32_t n_blocks, uint64_t content_bytes,
+                        uint32_t win_bits, uint32_t block_bits, uint8_t* __restrict__ frame, uint64_t capacity,
+                        uint64_t* __restrict__ copy_bytes, uint64_t* __restrict__ dense_off,
+                        uint64_t* __restrict__ idx_off, uint64_t* __restrict__ frame_bytes_out,
+                        int32_t* __restrict__ status_out) {
+    __shared__ uint64_t sums[256];
+    __shared__ int32_t first_err[256];
+    __shared__ int32_t verdict;
+    const uint32_t t = threadIdx.x;
+    const uint64_t per = ((uint64_t)n_blocks + 255) / 256;
+    const uint64_t b0 = t * per < n_blocks ? t * per : n_blocks;
+    const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+    uint64_t sum = 0;
+    int32_t bad = 0;
+    for (uint64_t b = b0; b < b1; b++) {
+        const uint64_t v = out_bytes[b];
+        if (bad == 0 && err[b] != 0) { bad = err[b]; }
+        if (bad == 0 && ((v & 7u) != 0 || (v >> 3) > 0xFFFFFFFFull)) { bad = kErrEINVAL; }
+        sum += v;
+    }
+    sums[t] = sum;
+    first_err[t] = bad;
+    __syncthreads();
+    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + 15) & ~(uint64_t)15;
+    if (t == 0) {
+        uint64_t run = 0;
+        int32_t st = 0;
+        for (int k = 0; k < 256; k++) {
+            const uint64_t v = sums[k];
+            sums[k] = run;
+            run += v;
+            if (st == 0) { st = first_err[k]; }
+        }
+        const uint64_t frame_bytes = payload_off + run;
+        if (st == 0 && frame_bytes > capacity) { st = kErrE2BIG; }
+        verdict = st;
+        *frame_bytes_out = frame_bytes;
+        *status_out = st;
+        idx_off[0] = st == 0 ? 32 : 0;
+        idx_off[1] = st == 0 ? 32 + 8 * (uint64_t)n_blocks : 0;
+        if (st == 0) {
+            uint32_t* const h = reinterpret_cast<uint32_t*>(frame);
+            h[0] = 0x465A5153u;                                    // "SQZF"
+            h[1] = 1u | (win_bits << 8) | (block_bits << 16);      // version, win_bits, block_bits, flags = 0
+            h[2] = (uint32_t)content_bytes; h[3] = (uint32_t)(content_bytes >> 32);
+            h[4] = (uint32_t)run; h[5] = (uint32_t)(run >> 32);
+            h[6] = n_blocks;
+            h[7] = 0u;                                             // index_crc: frame_seal_kernel
+            if ((n_blocks & 1u) != 0) { h[8 + 2 * (uint64_t)n_blocks] = 0u; h[9 + 2 * (uint64_t)n_blocks] = 0u; }
+        }
+    }
+    __syncthreads();
+    const bool ok = verdict == 0;
+    uint32_t* const index = reinterpret_cast<uint32_t*>(frame + 32);
+    uint64_t at = payload_off + sums[t];
+    for (uint64_t b = b0; b < b1; b++) {
+        const uint64_t v = out_bytes[b];
+        dense_off[b] = ok ? at : 0;
+        copy_bytes[b] = ok ? v : 0;
+        if (ok) { index[2 * b] = (uint32_t)(v >> 3); index[2 * b + 1] = crc[b]; }
+        at += v;
+    }
+    if (b1 == n_blocks && (b0 < b1 || t == 0)) { dense_off[n_blocks] = ok ? at : 0; }
+}
+
+void launch_frame_index(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
+                        uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint8_t* frame,
+                        uint64_t capacity, uint64_t* copy_bytes, uint64_t* dense_off, uint64_t* idx_off,
+                        uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_index_kernel, dim3(1), dim3(256), 0, stream, out_bytes, err, crc, n_blocks,
+                       content_bytes, win_bits, block_bits, frame, capacity, copy_bytes, dense_off, idx_off,
+                       frame_bytes_out, status_out);
+}
+
+// index_crc = crc32(header[0, 28) || index): the header's 28 bytes on the spot, joined with the index's
+// checksum (idx_crc, from crc32_blocks_kernel) by crc(A || B) = crc(A) * x^(8|B|) ^ crc(B)
+__global__ __launch_bounds__(64)
+void frame_seal_kernel(uint8_t* __restrict__ frame, const uint32_t* __restrict__ idx_crc, uint32_t n_blocks,
+                       const int32_t* __restrict__ status) {
+    const int lane = (int)threadIdx.x;
+    if (*status != 0) { return; }
+    const uint32_t h = crc32_small(frame, 28);
+    const uint32_t c = gf_mul(h, xpow8_wave(8 * (uint64_t)n_blocks, lane)) ^ *idx_crc;
+    if (lane == 0) { reinterpret_cast<uint32_t*>(frame)[7] = c; }
+}
+
+void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_blocks, const int32_t* status,
+                       hipStream_t stream) {
+    hipLaunchKernelGGL(frame_seal_kernel, dim3(1), dim3(64), 0, stream, frame, idx_crc, n_blocks, status);
+}
+
+// ---------------------------------------------------------------------------------------- decode side
+// One workgroup.  The caller read n_blocks and content_bytes from a host copy of the header and made sure
+// that avail covers header and index; idx_crc is the checksum of frame[32, 32 + 8 n) computed just before.
+// Checks that the device header says the same, every field's range, index_crc, the sum of stream_words
+// and that the payload lies inside avail.  Then in_off (absolute, from the start of the frame) and out_off
+// (from the start of block `first`) for blocks [first, first + n_sel).  On any failure *status is set and
+// every selected block gets a zero-length input and output: nothing behind the index is ever addressed.
+__global__ __launch_bounds__(256)
+void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
+                       uint64_t content_bytes, uint32_t first, uint32_t n_sel,
+                       const uint32_t* __restrict__ idx_crc, uint64_t* __restrict__ in_off,
+                       uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out) {
+    __shared__ uint64_t sums[256];
+    __shared__ int32_t verdict;
+    __shared__ uint32_t want_crc;
+    const uint32_t t = threadIdx.x;
+    const int lane = (int)(t & 63u);
+    if (t < 64) {                                  // wave 0, all of it: what index_crc has to be
+        const uint32_t h = crc32_small(frame, 28);
+        const uint32_t c = gf_mul(h, xpow8_wave(8 * (uint64_t)n_blocks, lane)) ^ *idx_crc;
+        if (lane == 0) { want_crc = c; }
+    }
+    const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
+    const uint64_t per = ((uint64_t)n_blocks + 255) / 256;
+    const uint64_t b0 = t * per < n_blocks ? t * per : n_blocks;
+    const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+    uint64_t sum = 0;
+    for (uint64_t b = b0; b < b1; b++) { sum += (uint64_t)index[2 * b] * 8; }
+    sums[t] = sum;
+    __syncthreads();
+    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + 15) & ~(uint64_t)15;
+    const uint32_t block_bits = frame[6];
+    if (t == 0) {
+        uint64_t run = 0;
+        bool beyond = false;                       // the streams add up to more than there is: stop adding (no wrap)
+        for (int k = 0; k < 256; k++) {
+            const uint64_t v = sums[k];            // < 2^59: at most 2^24 entries of less than 2^35 each
+            sums[k] = run;
+            if (v > avail || run > avail - v) { beyond = true; } else { run += v; }
+        }
+        int32_t st = 0;
+        const uint32_t win_bits = frame[5];
+        if (load_le32(frame) != 0x465A5153u || frame[4] != 1 || frame[7] != 0 || win_bits < 10 || win_bits > 15 ||
+            block_bits < 12 || block_bits > 24) {
+            st = kErrEINVAL;
+        } else {
+            const uint64_t bb = 1ull << block_bits;
+            const uint64_t want_n = content_bytes / bb + ((content_bytes & (bb - 1)) != 0 ? 1 : 0);
+            if (load_le64(frame + 8) != content_bytes || load_le32(frame + 24) != n_blocks || want_n != n_blocks ||
+                (uint64_t)first + n_sel > n_blocks) {
+                st = kErrEINVAL;
+            } else if (load_le32(frame + 28) != want_crc) {
+                st = kErrEILSEQ;
+            } else if (!beyond && load_le64(frame + 16) != run) {
+                st = kErrEINVAL;
+            } else if (beyond || payload_off > avail || run > avail - payload_off) {
+                st = kErrE2BIG;
+            }
+        }
+        verdict = st;
+        *status_out = st;
+    }
+    __syncthreads();
+    if (verdict != 0) {                            // refused: nothing below looks at the index again
+        for (uint64_t k = t; k <= n_sel; k += 256) { in_off[k] = 0; out_off[k] = 0; }
+        return;
+    }
+    const uint64_t bb = 1ull << block_bits;
+    const uint64_t base = (uint64_t)first * bb;
+    uint64_t at = payload_off + sums[t];
+    for (uint64_t b = b0; b < b1; b++) {
+        if (b >= first && b <= (uint64_t)first + n_sel) { in_off[b - first] = at; }
+        at += (uint64_t)index[2 * b] * 8;
+    }
+    if (b1 == n_blocks && (b0 < b1 || t == 0) && (uint64_t)first + n_sel == n_blocks) { in_off[n_sel] = at; }
+    for (uint64_t k = t; k <= n_sel; k += 256) {
+        const uint64_t o = (first + k) * bb < content_bytes ? (first + k) * bb : content_bytes;
+        out_off[k] = o - base;
+    }
+}
+
+void launch_frame_open(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                       uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
+                       uint64_t* out_off, int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_open_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
+                       first, n_sel, idx_crc, in_off, out_off, status_out);
+}
+
+// err[k] for the selected blocks: the frame's status where it was refused; EILSEQ where the decoder was
+// content but the bytes are not the ones that were checksummed; else what the decoder said
+__global__ __launch_bounds__(256)
+void frame_verify_kernel(const uint8_t* __restrict__ frame, uint32_t first, uint32_t n_sel,
+                         const uint32_t* __restrict__ crc, const int32_t* __restrict__ status,
+                         int32_t* __restrict__ err) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_sel) { return; }
+    const int32_t st = *status;
+    if (st != 0) { err[k] = st; return; }
+    const uint32_t stored = reinterpret_cast<const uint32_t*>(frame + 32)[2 * ((uint64_t)first + k) + 1];
+    if (err[k] == 0 && crc[k] != stored) { err[k] = kErrEILSEQ; }
+}
+
+void launch_frame_verify(const uint8_t* frame, uint32_t first, uint32_t n_sel, const uint32_t* crc,
+                         const int32_t* status, int32_t* err, hipStream_t stream) {
+    if (n_sel == 0) { return; }
+    hipLaunchKernelGGL(frame_verify_kernel, dim3((n_sel + 255) / 256), dim3(256), 0, stream,
+                       frame, first, n_sel, crc, status, err);
+}
+
+} // namespace sqzk

@@ -68,4 +68,27 @@ void launch_compact_blocks(const uint8_t* src, const uint64_t* src_off, const ui
                            uint32_t n_blocks, uint8_t* dst, const uint64_t* dst_off,
                            uint64_t avg_bytes, hipStream_t stream);
 
+// the SQZF frame container (frame.hip; format in include/sqz/sqz.h).
+// crc[b] = zlib.crc32(in[off[b] .. off[b+1])) for n ranges at arbitrary byte offsets; size_hint = the
+// largest range's size when the host knows it (0 = unknown): it only sizes the launch.
+void launch_crc32_blocks(const uint8_t* in, const uint64_t* off, uint32_t n_ranges, uint32_t* crc,
+                         uint64_t size_hint, hipStream_t stream);
+// in_off[k] = min(k * block_bytes, content_bytes), slab_off[k] = k * slab_bytes, k = 0..n_blocks
+void launch_frame_plan(uint32_t n_blocks, uint64_t block_bytes, uint64_t content_bytes, uint64_t slab_bytes,
+                       uint64_t* in_off, uint64_t* slab_off, hipStream_t stream);
+// encode: scan of the stream sizes -> header, index, padding, dense offsets (absolute in the frame),
+// frame size and status; then the index checksum into the header
+void launch_frame_index(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
+                        uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint8_t* frame,
+                        uint64_t capacity, uint64_t* copy_bytes, uint64_t* dense_off, uint64_t* idx_off,
+                        uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream);
+void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_blocks, const int32_t* status,
+                       hipStream_t stream);
+// decode: header and index checks, offsets of blocks [first, first + n_sel) for the decode kernels
+void launch_frame_open(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                       uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
+                       uint64_t* out_off, int32_t* status_out, hipStream_t stream);
+void launch_frame_verify(const uint8_t* frame, uint32_t first, uint32_t n_sel, const uint32_t* crc,
+                         const int32_t* status, int32_t* err, hipStream_t stream);
+
 } // namespace sqzk

@@ -1,0 +1,203 @@
+"""SQZF frames: one checksummed, seekable artifact for one large buffer (include/sqz/sqz.h).
+
+Host flavour (bytes in, bytes out) and a device flavour over torch tensors in the style of batch.py.
+Every byte of codec and checksum work happens in libsqz_amd.so; nothing is computed here.
+
+    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18]     compress a file
+    python -m sqz_amd.frame d IN OUT                                       decompress one
+    python -m sqz_amd.frame info IN                                        describe one
+"""
+import ctypes as C
+import errno
+
+from . import _native as N
+from .codec import SqzError, _raise
+
+HEADER_BYTES = 32
+
+
+def frame_bound(nbytes: int, block_bits: int = 18) -> int:
+    """worst-case size of the frame of `nbytes` bytes of content"""
+    return int(N.lib().sqz_frame_bound(nbytes, block_bits))
+
+
+def frame_info(frame) -> dict:
+    """The header's fields (sqz_frame_info), checked; with the index in reach, that too.
+    Host code: no device is touched."""
+    frame = bytes(frame)
+    fi = N.FrameInfo()
+    _raise(N.lib().sqz_frame_info(frame, len(frame), C.byref(fi)), "sqz_frame_info")
+    return {k: int(getattr(fi, k)) for k, _ in N.FrameInfo._fields_ if k != "reserved"}
+
+
+def compress_frame(data, win_bits: int = 15, block_bits: int = 18) -> bytes:
+    data = bytes(data)
+    cap = frame_bound(len(data), block_bits)
+    if cap == 0:
+        raise SqzError(errno.EINVAL, "sqz_frame_compress: block_bits out of range")
+    out = bytearray(cap)
+    n = C.c_uint64(0)
+    dst = (C.c_uint8 * cap).from_buffer(out)
+    _raise(N.lib().sqz_frame_compress(data, len(data), win_bits, block_bits, dst, cap, C.byref(n)),
+           "sqz_frame_compress")
+    del dst
+    return bytes(out[:n.value])
+
+
+def decompress_frame(frame, return_errors: bool = False):
+    """The content of a frame.  A block that fails raises SqzError with the first errno; its attribute
+    block_errors lists every block's.  return_errors=True returns (bytes, block_errors) instead: good
+    blocks are delivered, bad ones hold whatever the decoder produced."""
+    frame = bytes(frame)
+    fi = frame_info(frame[:HEADER_BYTES])
+    out = bytearray(max(fi["content_bytes"], 1))
+    dst = (C.c_uint8 * len(out)).from_buffer(out)
+    errs = (C.c_int32 * max(fi["n_blocks"], 1))()
+    n = C.c_uint64(0)
+    rc = N.lib().sqz_frame_decompress(frame, len(frame), dst, fi["content_bytes"], C.byref(n), errs)
+    del dst
+    block_errors = list(errs)[:fi["n_blocks"]]
+    if return_errors and (rc == 0 or any(block_errors)):
+        return bytes(out[:fi["content_bytes"]]), block_errors
+    if rc != 0:
+        e = SqzError(rc, f"sqz_frame_decompress: {errno.errorcode.get(rc, rc)}")
+        e.block_errors = block_errors
+        raise e
+    return bytes(out[:n.value])
+
+
+def read_range(frame, offset: int, length: int) -> bytes:
+    """content[offset : offset + length]: only the covering blocks are uploaded, decoded and verified"""
+    frame = bytes(frame)
+    content = frame_info(frame[:HEADER_BYTES])["content_bytes"]
+    out = bytearray(max(min(length, content), 1))            # a range that leaves the content is refused below
+    dst = (C.c_uint8 * len(out)).from_buffer(out)
+    rc = N.lib().sqz_frame_read(frame, len(frame), offset, length, dst)
+    del dst
+    _raise(rc, "sqz_frame_read")
+    return bytes(out[:length])
+
+
+# ---- device flavour (torch tensors hold the HBM) ------------------------------------------------
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream():
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def crc32_blocks(d_in, in_off, crc=None):
+    """zlib.crc32 of n ragged byte ranges of a uint8 tensor: in_off int64[n + 1] -> int32/uint32[n] on the device"""
+    import torch
+    n = in_off.numel() - 1
+    if crc is None:
+        crc = torch.zeros(max(n, 1), dtype=torch.int32, device=d_in.device)
+    _raise(N.lib().sqz_hip_crc32_blocks(_ptr(d_in), _ptr(in_off), n, _ptr(crc), _stream()), "sqz_hip_crc32_blocks")
+    return crc[:n]
+
+
+class FrameEncoder:
+    """Reusable device buffers for frames of up to `content_bytes` bytes at (win_bits, block_bits).
+    encode() enqueues and returns; frame_bytes / status / err are device tensors to read after a synchronise."""
+
+    def __init__(self, content_bytes: int, win_bits: int = 15, block_bits: int = 18, capacity: int = None,
+                 device="cuda"):
+        import torch
+        L = N.lib()
+        self.win_bits, self.block_bits, self.content_bytes = win_bits, block_bits, content_bytes
+        self.capacity = frame_bound(content_bytes, block_bits) if capacity is None else capacity
+        self.n_blocks = (content_bytes + (1 << block_bits) - 1) >> block_bits
+        self.frame = torch.empty(max(self.capacity, 16), dtype=torch.uint8, device=device)
+        self.frame_bytes = torch.zeros(1, dtype=torch.int64, device=device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+        self.err = torch.zeros(max(self.n_blocks, 1), dtype=torch.int32, device=device)
+        self.scratch_bytes = int(L.sqz_hip_frame_scratch_bytes(content_bytes, block_bits, 1))
+        self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=device)
+
+    def encode(self, d_in, content_bytes: int = None):
+        nbytes = d_in.numel() if content_bytes is None else content_bytes
+        if nbytes > self.content_bytes:
+            raise SqzError(errno.E2BIG, "FrameEncoder: more content than the buffers were made for")
+        _raise(N.lib().sqz_hip_frame_encode(
+            _ptr(d_in), nbytes, self.win_bits, self.block_bits, _ptr(self.frame), self.capacity,
+            _ptr(self.frame_bytes), _ptr(self.status), _ptr(self.err), _ptr(self.scratch), self.scratch_bytes,
+            _stream()), "sqz_hip_frame_encode")
+        return self.frame, self.frame_bytes, self.status, self.err
+
+    def result(self) -> bytes:
+        """synchronise and fetch the frame of the last encode(); raises on a frame-level status"""
+        import torch
+        torch.cuda.synchronize()
+        _raise(int(self.status.item()), "sqz_hip_frame_encode (status)")
+        return self.frame[:int(self.frame_bytes.item())].cpu().numpy().tobytes()
+
+
+_decode_scratch = {}
+
+
+def decode_frame(d_frame, d_out, info: dict = None, err=None, status=None, scratch=None):
+    """A device-resident frame into the caller's uint8 tensor.  `info` = frame_info() of the header (fetched
+    with one 32-byte copy when not given).  Enqueues and returns (err int32[n_blocks], status int32[1])."""
+    import torch
+    L = N.lib()
+    if info is None:
+        info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    n, content = info["n_blocks"], info["content_bytes"]
+    if d_out.numel() < content:
+        raise SqzError(errno.E2BIG, "decode_frame: d_out is smaller than the content")
+    if err is None:
+        err = torch.zeros(max(n, 1), dtype=torch.int32, device=d_out.device)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=d_out.device)
+    need = int(L.sqz_hip_frame_scratch_bytes(content, info["block_bytes"].bit_length() - 1, 0))
+    if scratch is None:
+        key = str(d_out.device)
+        scratch = _decode_scratch.get(key)
+        if scratch is None or scratch.numel() < need:
+            scratch = torch.empty(need, dtype=torch.uint8, device=d_out.device)
+            _decode_scratch[key] = scratch
+    _raise(L.sqz_hip_frame_decode(_ptr(d_frame), d_frame.numel(), n, content, _ptr(d_out), _ptr(err), _ptr(status),
+                                  _ptr(scratch), scratch.numel(), _stream()), "sqz_hip_frame_decode")
+    return err[:n], status
+
+
+# ---- file tool ----------------------------------------------------------------------------------
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m sqz_amd.frame", description="SQZF frames of files")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    c = sub.add_parser("c", help="compress IN to OUT")
+    c.add_argument("src")
+    c.add_argument("dst")
+    c.add_argument("--win-bits", type=int, default=15)
+    c.add_argument("--block-bits", type=int, default=18)
+    d = sub.add_parser("d", help="decompress IN to OUT")
+    d.add_argument("src")
+    d.add_argument("dst")
+    i = sub.add_parser("info", help="describe IN")
+    i.add_argument("src")
+    a = ap.parse_args(argv)
+    with open(a.src, "rb") as fh:
+        blob = fh.read()
+    try:
+        if a.cmd == "c":
+            out = compress_frame(blob, a.win_bits, a.block_bits)
+        elif a.cmd == "d":
+            out = decompress_frame(blob)
+        else:
+            for k, v in frame_info(blob).items():
+                print(f"{k}: {v}")
+            return 0
+    except SqzError as e:
+        print(f"sqz_amd.frame: {e}", flush=True)
+        return 1
+    with open(a.dst, "wb") as fh:
+        fh.write(out)
+    print(f"{a.src}: {len(blob)} -> {len(out)} bytes")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
