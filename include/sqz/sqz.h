@@ -343,26 +343,61 @@ SQZ_API int sqz_hip_pack_blocks(const void* d_slabs, const uint64_t* d_slab_off,
  * the same function.  frame_bytes = payload_off + payload_bytes: 32 for empty content.
  *
  * Errors: EINVAL a malformed header or argument, EILSEQ a checksum that does not match, E2BIG
- * a buffer (avail, capacity) that is too small.                                             */
+ * a buffer (avail, capacity) that is too small.
+ *
+ * Version 2 = version 1 with stored blocks: content that does not compress is carried as it is.
+ * Header, index entries, payload_off and both checksums keep their place and meaning; what differs:
+ *
+ *   4       1     version = 2
+ *   7       1     flags = SQZ_FRAME_STORED (bit 0).  A version-2 header always has a non-zero flags
+ *                 whose bits are all known: version 2 with flags 0 or with any of bits 1..7, and
+ *                 version 1 with any flag, are EINVAL.  A frame that uses no feature is version 1.
+ *   16      8     payload_bytes = sum of payload_words * 8 over all blocks, stored or not
+ *   32      8*n   index: per block { u32 payload_words | stored << 31 ; u32 content_crc }
+ *
+ * payload_words * 8 is the block's share of the payload (a stream is at most 2 * 2^24 + 1024 bytes,
+ * so bit 31 is free).  A stored block's share is its content followed by zeros up to the next
+ * multiple of 8: payload_words == ceil(length / 8) exactly, anything else is EINVAL; readers do not
+ * look at the padding.  content_crc covers the content and is verified for stored blocks too.
+ * Writer's rule, exact, so that any writer reproduces a frame byte for byte: block b is stored iff
+ * stream_bytes(b) >= length(b) -- streams are multiples of 8, so iff the stored form is not larger.
+ * A writer asked for SQZ_FRAME_STORED writes version 2 whether or not a block ends up stored: one
+ * byte of content is a stored block (8 >= 1), empty content a 32-byte version-2 header.  Worst case:
+ * frame_bytes <= pad16(32 + 8n) + round_up_8(content_bytes).                                 */
 enum {
     sqz_frame_header_bytes   = 32,
     sqz_frame_min_block_bits = 12,
     sqz_frame_max_block_bits = 24
 };
+enum { SQZ_FRAME_STORED = 1 };   /* flags: store a block raw when its stream is not smaller (version 2) */
 struct sqz_frame_info {
     uint64_t content_bytes, payload_bytes, payload_off, frame_bytes, block_bytes;
-    uint32_t n_blocks, win_bits, version, reserved;
+    uint32_t n_blocks, win_bits, version, reserved;     /* reserved: the header's flags */
+};
+/* one block of a frame: where its share of the payload lies (payload_off from the start of the
+ * frame), what it decodes to, and whether it is stored */
+struct sqz_frame_block {
+    uint64_t payload_off, payload_bytes, content_bytes;
+    uint32_t content_crc, stored;
 };
 
 /* Host code, no device is touched (like sqz_file_words). */
 /* worst-case frame_bytes: header + index + padding + sqz_bound per block; 0 for a block_bits
  * outside 12..24 */
 SQZ_API uint64_t sqz_frame_bound(uint64_t content_bytes, uint32_t block_bits);
+/* the same for a frame written with `flags`: sqz_frame_bound for 0; for SQZ_FRAME_STORED
+ * pad16(32 + 8n) + round_up_8(content_bytes); 0 for any other flags */
+SQZ_API uint64_t sqz_frame_bound_ex(uint64_t content_bytes, uint32_t block_bits, uint32_t flags);
 /* Parses and checks the header from the first `avail` bytes (E2BIG when avail < 32): magic,
  * version, flags, the ranges of win_bits / block_bits, n_blocks == ceil(content_bytes /
  * block_bytes), no overflow in 32 + 8n or frame_bytes (EINVAL).  When avail also covers the
  * index: index_crc (EILSEQ), and that the stream_words sum to payload_bytes / 8 (EINVAL).   */
 SQZ_API int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* out);
+/* Blocks [first, first + count) of a frame of either version, whose header, index and padding up to
+ * payload_off lie inside avail (E2BIG otherwise; every check of sqz_frame_info applies): what a
+ * caller needs to fetch one block's bytes from storage.  EINVAL when the range leaves the frame. */
+SQZ_API int sqz_frame_blocks(const uint8_t* frame, uint64_t avail, uint32_t first, uint32_t count,
+                             struct sqz_frame_block* out);
 
 /* Host buffers in, host buffers out (H2D + kernels + D2H inside, on a leased lane's stream).
  * The encode scratch is 8 bytes per input byte, so both directions work through the buffer in
@@ -380,6 +415,10 @@ SQZ_API int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_fram
  *   EINVAL when the range leaves the content.                                               */
 SQZ_API int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
                                uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes);
+/* compress_ex: flags = 0 is sqz_frame_compress; SQZ_FRAME_STORED writes version 2 (every block is still
+ * encoded: the rule needs its stream's size); other flags EINVAL.  Readers take both versions.  */
+SQZ_API int sqz_frame_compress_ex(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                                  uint32_t flags, uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes);
 SQZ_API int sqz_frame_decompress(const uint8_t* frame, uint64_t avail, uint8_t* data, uint64_t capacity,
                                  uint64_t* bytes, int32_t* block_err);
 SQZ_API int sqz_frame_read(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length,
@@ -402,6 +441,21 @@ SQZ_API int sqz_hip_frame_encode(const void* d_in, uint64_t content_bytes, uint3
                                  uint32_t block_bits, void* d_frame, uint64_t capacity,
                                  uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err,
                                  void* d_scratch, uint64_t scratch_bytes, void* stream);
+/* the _ex calls: flags as for sqz_frame_compress_ex.  A version-2 encode needs the scratch of
+ * sqz_hip_frame_scratch_bytes_ex(.., 1, SQZ_FRAME_STORED) (a mask more than version 1); a decode of
+ * either version needs what sqz_hip_frame_scratch_bytes(.., 0) says.  The frames equal the host
+ * flavour's byte for byte; a version-2 frame always fits sqz_frame_bound_ex bytes.
+ * sqz_hip_frame_decode cannot know the version without a host copy of the header, so it decodes
+ * every frame, version 1 included, with the mask-aware decode kernels and one launch of the copy
+ * kernel (all of whose workgroups leave at once for a version-1 frame): same results, but not the
+ * machine code that decoded a version-1 frame before.  The host calls know the version and decode
+ * a version-1 frame exactly as before.                                                         */
+SQZ_API uint64_t sqz_hip_frame_scratch_bytes_ex(uint64_t content_bytes, uint32_t block_bits, int encode,
+                                                uint32_t flags);
+SQZ_API int sqz_hip_frame_encode_ex(const void* d_in, uint64_t content_bytes, uint32_t win_bits,
+                                    uint32_t block_bits, uint32_t flags, void* d_frame, uint64_t capacity,
+                                    uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err,
+                                    void* d_scratch, uint64_t scratch_bytes, void* stream);
 SQZ_API int sqz_hip_frame_decode(const void* d_frame, uint64_t avail, uint32_t n_blocks,
                                  uint64_t content_bytes, void* d_out, int32_t* d_err, int32_t* d_status,
                                  void* d_scratch, uint64_t scratch_bytes, void* stream);
@@ -430,6 +484,7 @@ enum {
     SQZ_HIP_K_RC_DECODE = 8,      /* rc_decode_kernel  } (include/sqz/sqz_rc.h)       */
     SQZ_HIP_K_CRC32 = 9,          /* crc32_blocks_kernel } SQZF frames                */
     SQZ_HIP_K_FRAME_INDEX = 10,   /* frame_index_kernel / frame_open_kernel }         */
+    SQZ_HIP_K_RANGE_COPY = 11,    /* range_copy_kernel: stored blocks (SQZF version 2) */
     SQZ_HIP_KERNELS = 12
 };
 typedef struct sqz_hip_timing {

@@ -9,9 +9,10 @@ from .codec import (SqzError, bound, compress, decompress, device_info,  # noqa:
                     file_words, MIN_WIN_BITS, MAX_WIN_BITS)
 
 __all__ = ["SqzError", "bound", "compress", "decompress", "device_info", "file_words",
-           "MIN_WIN_BITS", "MAX_WIN_BITS", "compress_frame", "decompress_frame", "frame_info", "read_range"]
+           "MIN_WIN_BITS", "MAX_WIN_BITS", "compress_frame", "decompress_frame", "frame_info", "read_range",
+           "frame_blocks", "frame_bound"]
 
-_FRAME = ("compress_frame", "decompress_frame", "frame_info", "read_range")
+_FRAME = ("compress_frame", "decompress_frame", "frame_info", "read_range", "frame_blocks", "frame_bound")
 
 
 def __getattr__(name):

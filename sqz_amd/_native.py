@@ -30,7 +30,7 @@ class Sqz(C.Structure):
 KERNEL_NAMES = ["lz77_scan_kernel", "huffman_emit_kernel", "entropy_decode_kernel",
                 "index_sort_kernel", "index_match_kernel", "index_parse_kernel",
                 "lz_expand_kernel", "rc_encode_kernel", "rc_decode_kernel", "crc32_blocks_kernel",
-                "frame_index_kernel", "reserved"]
+                "frame_index_kernel", "range_copy_kernel"]
 
 
 class BlockStats(C.Structure):
@@ -60,6 +60,12 @@ class FrameInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("content_bytes", "payload_bytes", "payload_off", "frame_bytes",
                                           "block_bytes")] + \
                [(n, C.c_uint32) for n in ("n_blocks", "win_bits", "version", "reserved")]
+
+
+class FrameBlock(C.Structure):
+    """struct sqz_frame_block of include/sqz/sqz.h: one block's place in a frame."""
+    _fields_ = [(n, C.c_uint64) for n in ("payload_off", "payload_bytes", "content_bytes")] + \
+               [(n, C.c_uint32) for n in ("content_crc", "stored")]
 
 
 class Timing(C.Structure):
@@ -121,13 +127,19 @@ PROTOTYPES = {
     "sqz_hip_rc_encode_blocks": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "sqz_hip_rc_decode_blocks": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sqz_frame_bound": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "sqz_frame_bound_ex": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
     "sqz_frame_info": (C.c_int, [_vp, C.c_uint64, C.POINTER(FrameInfo)]),
+    "sqz_frame_blocks": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(FrameBlock)]),
+    "sqz_frame_compress_ex": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "sqz_frame_compress": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u64p]),
     "sqz_frame_decompress": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
     "sqz_frame_read": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp]),
     "sqz_hip_frame_scratch_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_int]),
     "sqz_hip_frame_encode": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp,
                                        _vp, C.c_uint64, _vp]),
+    "sqz_hip_frame_scratch_bytes_ex": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32]),
+    "sqz_hip_frame_encode_ex": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp,
+                                          _vp, _vp, C.c_uint64, _vp]),
     "sqz_hip_frame_decode": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64,
                                        _vp]),
     "sqz_hip_crc32_blocks": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),

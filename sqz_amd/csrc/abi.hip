@@ -488,6 +488,20 @@ uint64_t frame_blocks(uint64_t content_bytes, uint32_t block_bits) {
     return (content_bytes >> block_bits) + ((content_bytes & ((1ull << block_bits) - 1)) != 0 ? 1 : 0);
 }
 uint64_t frame_payload_off(uint64_t n_blocks) { return align_up(32 + 8 * n_blocks, 16); }
+// content bytes of block b
+uint64_t frame_block_len(uint64_t content_bytes, uint32_t block_bits, uint64_t b) {
+    const uint64_t bb = 1ull << block_bits, at = b * bb;
+    return at >= content_bytes ? 0 : (content_bytes - at < bb ? content_bytes - at : bb);
+}
+// block b's share of the payload in words: in version 2 bit 31 of the entry is the stored bit
+uint32_t frame_entry_words(const uint8_t* frame, uint32_t version, uint64_t b) {
+    const uint32_t e = get_le32(frame + 32 + 8 * b);
+    return version >= 2 ? e & 0x7FFFFFFFu : e;
+}
+bool frame_entry_stored(const uint8_t* frame, uint32_t version, uint64_t b) {
+    return version >= 2 && (get_le32(frame + 32 + 8 * b) >> 31) != 0;
+}
+bool frame_flags_ok(uint32_t flags) { return flags == 0 || flags == (uint32_t)SQZ_FRAME_STORED; }
 
 // content bytes a host call works through per pass (whole blocks, one at least)
 uint64_t frame_pass_blocks(uint64_t block_bytes) {
@@ -500,9 +514,12 @@ uint64_t frame_pass_blocks(uint64_t block_bytes) {
 
 // where the pieces of a device call's scratch lie (every piece 256-byte aligned)
 struct FrameScratch {
-    uint64_t in_off, out_off, out_bytes, copy_bytes, dense_off, crc, misc, slabs, codec, codec_bytes, total;
+    uint64_t in_off, out_off, out_bytes, copy_bytes, dense_off, crc, misc, slabs, codec, codec_bytes, stored, total;
 };
-FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_bytes, bool encode) {
+// store: an encode that may store blocks has a mask of its own.  A decode keeps its mask in `crc`: the open
+// kernel writes it, the decode and copy kernels read it, and only then, on the same stream, do the checksums
+// of the output land there -- so a decode of either version needs exactly the scratch it always did.
+FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_bytes, bool encode, bool store = false) {
     FrameScratch L = {};
     uint64_t at = 0;
     auto take = [&at](uint64_t bytes) { const uint64_t r = at; at += align_up(bytes, 256); return r; };
@@ -520,6 +537,7 @@ FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_byt
         L.codec_bytes = sqz_hip_decode_scratch_bytes((uint32_t)n, content_bytes);
     }
     L.codec = take(L.codec_bytes);
+    L.stored = encode && store ? take(n * 4 + 4) : L.crc;
     L.total = at;
     return L;
 }
@@ -527,12 +545,14 @@ FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_byt
 // the device side of a frame encode: everything enqueued on st, nothing waits
 int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
                      uint8_t* d_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
-                     int32_t* d_err, uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st) {
+                     int32_t* d_err, uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t flags = 0) {
     const uint64_t bb = 1ull << block_bits, n64 = frame_blocks(content_bytes, block_bits);
     if (n64 > 0xFFFFFFFFull) { return EINVAL; }
     const uint32_t n = (uint32_t)n64;
     const uint64_t slab = sqz_bound(bb);
-    const FrameScratch L = frame_scratch(n, content_bytes, slab, true);
+    const bool store = (flags & SQZ_FRAME_STORED) != 0;
+    const FrameScratch L = frame_scratch(n, content_bytes, slab, true, store);
+    uint32_t* stored = (uint32_t*)(scratch + L.stored);
     if (scratch_bytes < L.total) { return EINVAL; }
     uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
     uint64_t* slab_off = (uint64_t*)(scratch + L.out_off);
@@ -554,13 +574,22 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
                    scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st);
     }
     { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
-      sqzk::launch_frame_index(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, d_frame, capacity,
-                               copy_bytes, dense_off, idx_off, d_frame_bytes, d_status, st); }
+      if (store) {
+          sqzk::launch_frame_index_v2(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, d_frame, capacity,
+                                      copy_bytes, dense_off, stored, idx_off, d_frame_bytes, d_status, st);
+      } else {
+          sqzk::launch_frame_index(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, d_frame, capacity,
+                                   copy_bytes, dense_off, idx_off, d_frame_bytes, d_status, st);
+      } }
     { SpanGuard g(st, SQZ_HIP_K_CRC32);
       sqzk::launch_crc32_blocks(d_frame, idx_off, 1, idx_crc, 8 * (uint64_t)n, st); }
     sqzk::launch_frame_seal(d_frame, idx_crc, n, d_status, st);
     if (n > 0) {
         sqzk::launch_compact_blocks(scratch + L.slabs, slab_off, copy_bytes, n, d_frame, dense_off, bb / 2, st);
+        if (store) {                                        // the stored blocks' content, where the index says
+            SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+            sqzk::launch_range_copy(d_in, in_off, d_frame, dense_off, in_off, stored, n, true, bb, st);
+        }
     }
     return hip_errno(hipGetLastError());
 }
@@ -568,12 +597,13 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
 // the device side of a frame decode, blocks [first, first + n_sel) into d_out (block `first` at its start)
 int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_t content_bytes, uint32_t first,
                      uint32_t n_sel, uint64_t sel_bytes, uint8_t* d_out, int32_t* d_err, int32_t* d_status,
-                     uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st) {
+                     uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t version) {
     const FrameScratch L = frame_scratch(n_sel, sel_bytes, 0, false);
     if (scratch_bytes < L.total || avail < 32 + 8 * (uint64_t)n) { return scratch_bytes < L.total ? EINVAL : E2BIG; }
     uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
     uint64_t* out_off = (uint64_t*)(scratch + L.out_off);
     uint32_t* crc = (uint32_t*)(scratch + L.crc);
+    uint32_t* stored = (uint32_t*)(scratch + L.stored);     // the same words as crc, one after the other (frame_scratch)
     uint64_t* idx_off = (uint64_t*)(scratch + L.misc);
     uint32_t* idx_crc = (uint32_t*)(scratch + L.misc + 16);
     uint64_t* spare = (uint64_t*)(scratch + L.misc + 32);
@@ -582,15 +612,24 @@ int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_
     { SpanGuard g(st, SQZ_HIP_K_CRC32);
       sqzk::launch_crc32_blocks(d_frame + 32, idx_off, 1, idx_crc, 8 * (uint64_t)n, st); }
     { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
-      sqzk::launch_frame_open(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, in_off, out_off, d_status, st); }
+      sqzk::launch_frame_open_v2(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, in_off, out_off, stored,
+                                 d_status, st); }
+    // version: what a host copy of the header said, 0 when the caller has none (the device flavour).  Only a frame
+    // known to be version 1 goes without the mask, and then without the copy launch
+    const uint32_t* const skip = version == 1 ? nullptr : stored;
     if (n_sel > 0) {
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + align_up((uint64_t)n_sel * 4, 256));
         { SpanGuard g(st, SQZ_HIP_K_ENTROPY_DECODE);
           sqzk::launch_entropy_decode(d_frame, in_off, out_off, tokens, counts, d_err, nullptr, n_sel, 0,
-                                      decode_waves_for(n_sel), st); }
+                                      decode_waves_for(n_sel), st, skip); }
         { SpanGuard g(st, SQZ_HIP_K_LZ_EXPAND);
-          sqzk::launch_lz_expand(tokens, counts, d_out, out_off, n_sel, st); }
+          sqzk::launch_lz_expand(tokens, counts, d_out, out_off, n_sel, st, skip); }
+        if (skip != nullptr) {
+            SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+            sqzk::launch_range_copy(d_frame, in_off, d_out, out_off, out_off, stored, n_sel, false,
+                                    (sel_bytes + n_sel - 1) / n_sel, st);
+        }
         { SpanGuard g(st, SQZ_HIP_K_CRC32);
           sqzk::launch_crc32_blocks(d_out, out_off, n_sel, crc, (sel_bytes + n_sel - 1) / n_sel, st); }
         sqzk::launch_frame_verify(d_frame, first, n_sel, crc, d_status, d_err, st);
@@ -608,7 +647,7 @@ int frame_decode_host(Lane& c, hipStream_t st, const uint8_t* frame, const struc
     const uint64_t bb = fi.block_bytes, n = fi.n_blocks;
     std::vector<uint64_t> pre(n + 1);
     pre[0] = 0;
-    for (uint64_t b = 0; b < n; b++) { pre[b + 1] = pre[b] + 8 * (uint64_t)get_le32(frame + 32 + 8 * b); }
+    for (uint64_t b = 0; b < n; b++) { pre[b + 1] = pre[b] + 8 * (uint64_t)frame_entry_words(frame, fi.version, b); }
     int e;
     if ((e = c.dense.reserve(fi.frame_bytes + 16)) || (e = c.misc.reserve(256))) { return e; }
     uint8_t* const d_frame = (uint8_t*)c.dense.p;
@@ -626,7 +665,7 @@ int frame_decode_host(Lane& c, hipStream_t st, const uint8_t* frame, const struc
         }
         if ((e = frame_decode_dev(d_frame, fi.frame_bytes, (uint32_t)n, fi.content_bytes, (uint32_t)p0, (uint32_t)pn,
                                   c1 - c0, (uint8_t*)c.out.p, (int32_t*)c.err.p, (int32_t*)c.misc.p,
-                                  (uint8_t*)c.work_a.p, L.total, st)) != 0) { return e; }
+                                  (uint8_t*)c.work_a.p, L.total, st, fi.version)) != 0) { return e; }
         errs.resize(pn);
         int32_t status = 0;
         HIP_TRY(hipMemcpyAsync(errs.data(), c.err.p, pn * 4, hipMemcpyDeviceToHost, st));
@@ -1212,9 +1251,10 @@ int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* 
     if (frame == NULL || out == NULL) { return EINVAL; }
     if (avail < 32) { return E2BIG; }
     const uint32_t win_bits = frame[5], block_bits = frame[6];
-    if (get_le32(frame) != 0x465A5153u || frame[4] != 1 || frame[7] != 0 || !frame_params_ok(win_bits, block_bits)) {
-        return EINVAL;
-    }
+    // version 1 has no flags; version 2 has at least one, and only known ones
+    const uint32_t version = frame[4], flags = frame[7];
+    const bool version_ok = (version == 1 && flags == 0) || (version == 2 && flags == (uint32_t)SQZ_FRAME_STORED);
+    if (get_le32(frame) != 0x465A5153u || !version_ok || !frame_params_ok(win_bits, block_bits)) { return EINVAL; }
     const uint64_t content = get_le64(frame + 8), payload = get_le64(frame + 16);
     const uint64_t n = get_le32(frame + 24);
     if (frame_blocks(content, block_bits) != n || (payload & 7u) != 0) { return EINVAL; }
@@ -1227,22 +1267,64 @@ int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* 
     out->block_bytes = 1ull << block_bits;
     out->n_blocks = (uint32_t)n;
     out->win_bits = win_bits;
-    out->version = frame[4];
-    out->reserved = 0;
+    out->version = version;
+    out->reserved = flags;
     if (avail >= 32 + 8 * n) {                              // the index is there: check it too
         const uint32_t crc = host_crc32(host_crc32(0, frame, 28), frame + 32, 8 * n);
         if (crc != get_le32(frame + 28)) { return EILSEQ; }
         uint64_t words = 0;
-        for (uint64_t b = 0; b < n; b++) { words += get_le32(frame + 32 + 8 * b); }    // < 2^64: n, words < 2^32
+        for (uint64_t b = 0; b < n; b++) {                  // < 2^64: n, words < 2^32
+            const uint32_t w = frame_entry_words(frame, version, b);
+            if (frame_entry_stored(frame, version, b) &&
+                w != (frame_block_len(content, block_bits, b) + 7) / 8) { return EINVAL; }
+            words += w;
+        }
         if (words != payload / 8) { return EINVAL; }
     }
     return 0;
 }
 
+int sqz_frame_blocks(const uint8_t* frame, uint64_t avail, uint32_t first, uint32_t count,
+                     struct sqz_frame_block* out) {
+    struct sqz_frame_info fi;
+    const int e = frame_check_host(frame, avail, &fi);
+    if (e != 0) { return e; }
+    if ((uint64_t)first + count > fi.n_blocks || (out == NULL && count > 0)) { return EINVAL; }
+    const uint32_t block_bits = frame[6];
+    uint64_t at = fi.payload_off;
+    for (uint64_t b = 0; b < (uint64_t)first + count; b++) {
+        const uint64_t share = 8 * (uint64_t)frame_entry_words(frame, fi.version, b);
+        if (b >= first) {
+            struct sqz_frame_block& o = out[b - first];
+            o.payload_off = at;
+            o.payload_bytes = share;
+            o.content_bytes = frame_block_len(fi.content_bytes, block_bits, b);
+            o.content_crc = get_le32(frame + 32 + 8 * b + 4);
+            o.stored = frame_entry_stored(frame, fi.version, b) ? 1u : 0u;
+        }
+        at += share;
+    }
+    return 0;
+}
+
+uint64_t sqz_frame_bound_ex(uint64_t content_bytes, uint32_t block_bits, uint32_t flags) {
+    if (!frame_flags_ok(flags)) { return 0; }
+    if (flags == 0) { return sqz_frame_bound(content_bytes, block_bits); }
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits) { return 0; }
+    // no block takes more than its content rounded up to 8 bytes, and all but the last are multiples of 8
+    return frame_payload_off(frame_blocks(content_bytes, block_bits)) + align_up(content_bytes, 8);
+}
+
 int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
                        uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
+    return sqz_frame_compress_ex(data, bytes, win_bits, block_bits, 0, frame, capacity, frame_bytes);
+}
+
+int sqz_frame_compress_ex(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits, uint32_t flags,
+                          uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
     if (frame_bytes == NULL || (frame == NULL && capacity > 0) || (data == NULL && bytes > 0) ||
-        !frame_params_ok(win_bits, block_bits)) { return EINVAL; }
+        !frame_params_ok(win_bits, block_bits) || !frame_flags_ok(flags)) { return EINVAL; }
+    const bool store = (flags & SQZ_FRAME_STORED) != 0;
     const uint64_t bb = 1ull << block_bits, n = frame_blocks(bytes, block_bits);
     if (n > 0xFFFFFFFFull) { return EINVAL; }
     const uint64_t payload_off = frame_payload_off(n), slab = sqz_bound(bb);
@@ -1282,18 +1364,32 @@ int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, u
             HIP_TRY(hipMemcpyAsync(crc.data(), c.crc.p, (size_t)pn * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             dense_off[0] = 0;
+            bool any_stored = false;
             for (uint32_t b = 0; b < pn; b++) {
                 if (err[b] != 0) { return err[b]; }
-                if ((out_bytes[b] & 7u) != 0 || out_bytes[b] / 8 > 0xFFFFFFFFull) { return EINVAL; }
-                dense_off[b + 1] = dense_off[b] + out_bytes[b];
-                put_le32(head.data() + 32 + 8 * (p0 + b), (uint32_t)(out_bytes[b] / 8));
+                if ((out_bytes[b] & 7u) != 0 || out_bytes[b] / 8 > (store ? 0x7FFFFFFFull : 0xFFFFFFFFull)) { return EINVAL; }
+                const uint64_t len = frame_block_len(bytes, block_bits, p0 + b);
+                const bool st_b = store && out_bytes[b] >= len;     // the writer's rule (include/sqz/sqz.h)
+                const uint64_t share = st_b ? align_up(len, 8) : out_bytes[b];
+                dense_off[b + 1] = dense_off[b] + share;
+                put_le32(head.data() + 32 + 8 * (p0 + b), (uint32_t)(share / 8) | (st_b ? 0x80000000u : 0u));
                 put_le32(head.data() + 32 + 8 * (p0 + b) + 4, crc[b]);
+                crc[b] = st_b ? 1u : 0u;                            // (the checksum is in the index): the copy's mask
+                if (st_b) { out_bytes[b] = 0; any_stored = true; }  // from here on: what the compaction moves
             }
             const uint64_t dense_total = dense_off[pn];
             fits = fits && dense_total <= capacity - payload_off - payload;
             if (fits && dense_total > 0) {                  // the pass's streams leave as one transfer to their place
                 if ((e = c.dense.reserve(dense_total + 16)) || (e = c.dense_off.reserve(((size_t)pn + 1) * 8))) { return e; }
                 HIP_TRY(hipMemcpyAsync(c.dense_off.p, dense_off.data(), ((size_t)pn + 1) * 8, hipMemcpyHostToDevice, st));
+                if (any_stored) {                           // the stored blocks: no stream to move, their content instead
+                    HIP_TRY(hipMemcpyAsync(c.out_bytes.p, out_bytes.data(), (size_t)pn * 8, hipMemcpyHostToDevice, st));
+                    HIP_TRY(hipMemcpyAsync(c.crc.p, crc.data(), (size_t)pn * 4, hipMemcpyHostToDevice, st));
+                    SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+                    sqzk::launch_range_copy((const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, (uint8_t*)c.dense.p,
+                                            (const uint64_t*)c.dense_off.p, (const uint64_t*)c.in_off.p,
+                                            (const uint32_t*)c.crc.p, pn, true, bb, st);
+                }
                 sqzk::launch_compact_blocks((const uint8_t*)c.out.p, (const uint64_t*)c.out_off.p,
                                             (const uint64_t*)c.out_bytes.p, pn, (uint8_t*)c.dense.p,
                                             (const uint64_t*)c.dense_off.p, dense_total / pn, st);
@@ -1308,7 +1404,7 @@ int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, u
     if (!fits) { return E2BIG; }
     uint8_t* h = head.data();
     put_le32(h, 0x465A5153u);
-    h[4] = 1; h[5] = (uint8_t)win_bits; h[6] = (uint8_t)block_bits; h[7] = 0;
+    h[4] = store ? 2 : 1; h[5] = (uint8_t)win_bits; h[6] = (uint8_t)block_bits; h[7] = (uint8_t)flags;
     put_le64(h + 8, bytes);
     put_le64(h + 16, payload);
     put_le32(h + 24, (uint32_t)n);
@@ -1352,7 +1448,7 @@ int sqz_frame_read(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64
     if (length == 0) { return 0; }
     const uint64_t bb = fi.block_bytes, b_first = offset / bb, b_end = (offset + length - 1) / bb + 1;
     uint64_t words = 0;                                     // the covering streams must be inside avail
-    for (uint64_t b = 0; b < b_end; b++) { words += get_le32(frame + 32 + 8 * b); }
+    for (uint64_t b = 0; b < b_end; b++) { words += frame_entry_words(frame, fi.version, b); }
     if (8 * words > avail - fi.payload_off) { return E2BIG; }
     if ((e = device_ready()) != 0) { return e; }
     LaneLease lease;
@@ -1375,16 +1471,33 @@ uint64_t sqz_hip_frame_scratch_bytes(uint64_t content_bytes, uint32_t block_bits
     return frame_scratch(n, content_bytes, sqz_bound(1ull << block_bits), encode != 0).total;
 }
 
+uint64_t sqz_hip_frame_scratch_bytes_ex(uint64_t content_bytes, uint32_t block_bits, int encode, uint32_t flags) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        !frame_flags_ok(flags)) { return 0; }
+    const uint64_t n = frame_blocks(content_bytes, block_bits);
+    return frame_scratch(n, content_bytes, sqz_bound(1ull << block_bits), encode != 0,
+                         (flags & SQZ_FRAME_STORED) != 0).total;
+}
+
 int sqz_hip_frame_encode(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
                          void* d_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
                          int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return sqz_hip_frame_encode_ex(d_in, content_bytes, win_bits, block_bits, 0, d_frame, capacity, d_frame_bytes,
+                                   d_status, d_err, d_scratch, scratch_bytes, stream);
+}
+
+int sqz_hip_frame_encode_ex(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
+                            uint32_t flags, void* d_frame, uint64_t capacity, uint64_t* d_frame_bytes,
+                            int32_t* d_status, int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!frame_flags_ok(flags)) { return EINVAL; }
     if (!frame_params_ok(win_bits, block_bits) || (d_in == NULL && content_bytes > 0) || d_frame == NULL ||
         ((uintptr_t)d_frame & 15u) != 0 || d_frame_bytes == NULL || d_status == NULL ||
         (d_err == NULL && content_bytes > 0) || d_scratch == NULL || ((uintptr_t)d_scratch & 15u) != 0) { return EINVAL; }
     const int e = device_ready();
     if (e != 0) { return e; }
     return frame_encode_dev((const uint8_t*)d_in, content_bytes, win_bits, block_bits, (uint8_t*)d_frame, capacity,
-                            d_frame_bytes, d_status, d_err, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream);
+                            d_frame_bytes, d_status, d_err, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
+                            flags);
 }
 
 int sqz_hip_frame_decode(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
@@ -1399,7 +1512,8 @@ int sqz_hip_frame_decode(const void* d_frame, uint64_t avail, uint32_t n_blocks,
     const int e = device_ready();
     if (e != 0) { return e; }
     return frame_decode_dev((const uint8_t*)d_frame, avail, n_blocks, content_bytes, 0, n_blocks, content_bytes,
-                            (uint8_t*)d_out, d_err, d_status, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream);
+                            (uint8_t*)d_out, d_err, d_status, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
+                            0);
 }
 
 int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t* d_crc, void* stream) {

@@ -99,6 +99,9 @@ __device__ __forceinline__ int peek_symbol(BitSource& r, const T& t) {
 // bump_batch then establishes for a prefix of them; the token the step stops at takes the
 // one-at-a-time updates (and, if it is an NYT escape or malformed input, is decoded again
 // from its own bit position), so errors and updates are the reference's.
+// kSkip: the instantiation that looks at `skip` (SQZF stored blocks).  Without it the kernel is, instruction for
+// instruction, the one that never had the argument: a batch without a mask pays nothing for the feature.
+template <bool kSkip>
 __global__ __launch_bounds__(kWave, 4)          // four waves per SIMD: 16 streams per CU (the LDS allows as many)
 void entropy_decode_kernel(const uint8_t* __restrict__ in,
                            const uint64_t* __restrict__ in_off,
@@ -108,11 +111,18 @@ void entropy_decode_kernel(const uint8_t* __restrict__ in,
                            int32_t* __restrict__ err_out,
                            uint64_t* __restrict__ end_bit,   // optional: bit position after the last symbol
                            uint32_t n_blocks,
-                           uint64_t start_bit) {
+                           uint64_t start_bit,
+                           const uint32_t* __restrict__ skip) {   // optional: blocks that are not streams (SQZF stored blocks)
     __shared__ DecodeLds lds;
     const int lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
     if (b >= n_blocks) { return; }
+    if constexpr (kSkip) {
+        if (skip[b] != 0) {                        // (the whole workgroup) no tokens, no error, nothing read or written
+            if (lane == 0) { tok_count[b] = 0; err_out[b] = 0; }
+            return;
+        }
+    }
 
     LitTree lit; PosTree pos;
     lit.lds = &lds.tree; lit.code = nullptr; lit.lut = lds.luts.lit;
@@ -533,7 +543,7 @@ struct DecodeMwLds {
     MwRound    round[2];
 };
 
-template <int W>
+template <int W, bool kSkip>
 __global__ __launch_bounds__(kWave * W, 4)      // 128 VGPRs: 16 waves per CU = 16 / W streams
 void entropy_decode_mw_kernel(const uint8_t* __restrict__ in,
                               const uint64_t* __restrict__ in_off,
@@ -543,12 +553,19 @@ void entropy_decode_mw_kernel(const uint8_t* __restrict__ in,
                               int32_t* __restrict__ err_out,
                               uint64_t* __restrict__ end_bit,
                               uint32_t n_blocks,
-                              uint64_t start_bit) {
+                              uint64_t start_bit,
+                              const uint32_t* __restrict__ skip) {
     __shared__ DecodeMwLds<W> lds;
     const int lane = (int)(threadIdx.x & (kWave - 1));
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t b = blockIdx.x;
     if (b >= n_blocks) { return; }                 // (the whole workgroup)
+    if constexpr (kSkip) {
+        if (skip[b] != 0) {                        // (the whole workgroup) as in entropy_decode_kernel
+            if (threadIdx.x == 0) { tok_count[b] = 0; err_out[b] = 0; }
+            return;
+        }
+    }
 
     LitTree lit; PosTree pos;
     lit.lds = &lds.tree; lit.code = nullptr; lit.lut = lds.luts.lit;
@@ -1033,15 +1050,20 @@ __device__ __forceinline__ uint8_t load_l2(const uint8_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+template <bool kSkip>
 __global__ __launch_bounds__(kWave, 4)          // four waves per SIMD: 16 streams per CU (the LDS allows as many)
 void lz_expand_kernel(const uint32_t* __restrict__ tokens,
                          const uint32_t* __restrict__ tok_count,
                          uint8_t* __restrict__ out,
                          const uint64_t* __restrict__ out_off,
-                         uint32_t n_blocks) {
+                         uint32_t n_blocks,
+                         const uint32_t* __restrict__ skip) {       // optional, as in entropy_decode_kernel
     const int lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
     if (b >= n_blocks) { return; }
+    if constexpr (kSkip) {
+        if (skip[b] != 0) { return; }
+    }
     uint8_t* dst = out + out_off[b];
     const uint32_t* tok = tokens + out_off[b];
     const uint32_t count = tok_count[b];      // tokens decoded before an error are still expanded
@@ -1099,31 +1121,53 @@ void lz_expand_kernel(const uint32_t* __restrict__ tokens,
     }
 }
 
-void launch_entropy_decode(const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off,
-                           uint32_t* tokens, uint32_t* tok_count, int32_t* err, uint64_t* end_bit,
-                           uint32_t n_blocks, uint64_t start_bit, int waves, hipStream_t stream) {
-    if (n_blocks == 0) { return; }
+namespace {
+template <bool kSkip>
+void launch_entropy_decode_as(const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off,
+                              uint32_t* tokens, uint32_t* tok_count, int32_t* err, uint64_t* end_bit,
+                              uint32_t n_blocks, uint64_t start_bit, int waves, hipStream_t stream,
+                              const uint32_t* skip) {
     // waves per stream: 1 when the batch fills the chip by itself (16 streams per CU), 2 / 4 when it does not
     if (waves >= 8) {
-        hipLaunchKernelGGL(entropy_decode_mw_kernel<8>, dim3(n_blocks), dim3(kWave * 8), 0, stream,
-                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit);
+        hipLaunchKernelGGL((entropy_decode_mw_kernel<8, kSkip>), dim3(n_blocks), dim3(kWave * 8), 0, stream,
+                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip);
     } else if (waves >= 4) {
-        hipLaunchKernelGGL(entropy_decode_mw_kernel<4>, dim3(n_blocks), dim3(kWave * 4), 0, stream,
-                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit);
+        hipLaunchKernelGGL((entropy_decode_mw_kernel<4, kSkip>), dim3(n_blocks), dim3(kWave * 4), 0, stream,
+                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip);
     } else if (waves >= 2) {
-        hipLaunchKernelGGL(entropy_decode_mw_kernel<2>, dim3(n_blocks), dim3(kWave * 2), 0, stream,
-                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit);
+        hipLaunchKernelGGL((entropy_decode_mw_kernel<2, kSkip>), dim3(n_blocks), dim3(kWave * 2), 0, stream,
+                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip);
     } else {
-        hipLaunchKernelGGL(entropy_decode_kernel, dim3(n_blocks), dim3(kWave), 0, stream,
-                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit);
+        hipLaunchKernelGGL(entropy_decode_kernel<kSkip>, dim3(n_blocks), dim3(kWave), 0, stream,
+                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip);
+    }
+}
+} // namespace
+
+void launch_entropy_decode(const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off,
+                           uint32_t* tokens, uint32_t* tok_count, int32_t* err, uint64_t* end_bit,
+                           uint32_t n_blocks, uint64_t start_bit, int waves, hipStream_t stream,
+                           const uint32_t* skip) {
+    if (n_blocks == 0) { return; }
+    if (skip != nullptr) {
+        launch_entropy_decode_as<true>(in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, waves,
+                                       stream, skip);
+    } else {
+        launch_entropy_decode_as<false>(in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, waves,
+                                        stream, skip);
     }
 }
 
 void launch_lz_expand(const uint32_t* tokens, const uint32_t* tok_count, uint8_t* out,
-                      const uint64_t* out_off, uint32_t n_blocks, hipStream_t stream) {
+                      const uint64_t* out_off, uint32_t n_blocks, hipStream_t stream, const uint32_t* skip) {
     if (n_blocks == 0) { return; }
-    hipLaunchKernelGGL(lz_expand_kernel, dim3(n_blocks), dim3(kWave), 0, stream,
-                       tokens, tok_count, out, out_off, n_blocks);
+    if (skip != nullptr) {
+        hipLaunchKernelGGL(lz_expand_kernel<true>, dim3(n_blocks), dim3(kWave), 0, stream,
+                           tokens, tok_count, out, out_off, n_blocks, skip);
+    } else {
+        hipLaunchKernelGGL(lz_expand_kernel<false>, dim3(n_blocks), dim3(kWave), 0, stream,
+                           tokens, tok_count, out, out_off, n_blocks, skip);
+    }
 }
 
 } // namespace sqzk

@@ -116,6 +116,20 @@ __device__ __forceinline__ uint32_t crc32_small(const uint8_t* p, uint32_t n) {
     return c ^ 0xFFFFFFFFu;
 }
 
+// SQZF version 2 (include/sqz/sqz.h): flags bit 0, bit 31 of an index entry's first word
+constexpr uint32_t kFrameStored = 1u;
+constexpr uint32_t kStoredBit = 0x80000000u;
+
+// content bytes of block b
+__device__ __forceinline__ uint64_t block_len(uint64_t b, uint64_t bb, uint64_t content_bytes) {
+    const uint64_t at = b * bb;
+    return at >= content_bytes ? 0 : (content_bytes - at < bb ? content_bytes - at : bb);
+}
+// the writer's rule: a block whose stream is not smaller than its content is stored, padded to 8 bytes
+__device__ __forceinline__ uint64_t payload_share(uint64_t stream_bytes, uint64_t len) {
+    return stream_bytes >= len ? (len + 7) & ~(uint64_t)7 : stream_bytes;
+}
+
 __device__ __forceinline__ uint32_t load_le32(const uint8_t* p) {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
@@ -250,13 +264,18 @@ void launch_frame_plan(uint32_t n_blocks, uint64_t block_bytes, uint64_t content
 // does not fit `capacity`, or a block the encoder failed, leaves the frame untouched: copy_bytes[] = 0 makes
 // the compaction a no-op, idx_off = {0, 0} the index checksum an empty range.  The index_crc field is
 // written by frame_seal_kernel once the index has been summed.
+//
+// flags = SQZ_FRAME_STORED writes version 2: block b is stored iff out_bytes[b] >= its length.  A stored block
+// takes round_up_8(length) bytes of the payload in the same scan, gets copy_bytes[b] = 0 (the compaction passes
+// it by) and stored[b] = 1 (range_copy_kernel moves its content); stored[] is all zeros on a refusal.  With
+// flags = 0 stored is not touched and may be null.
 __global__ __launch_bounds__(256)
 void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
                         const uint32_t* __restrict__ crc, uint32_t n_blocks, uint64_t content_bytes,
                         uint32_t win_bits, uint32_t block_bits, uint8_t* __restrict__ frame, uint64_t capacity,
                         uint64_t* __restrict__ copy_bytes, uint64_t* __restrict__ dense_off,
                         uint64_t* __restrict__ idx_off, uint64_t* __restrict__ frame_bytes_out,
-                        int32_t* __restrict__ status_out) {
+                        int32_t* __restrict__ status_out, uint32_t flags, uint32_t* __restrict__ stored) {
     __shared__ uint64_t sums[256];
     __shared__ int32_t first_err[256];
     __shared__ int32_t verdict;
@@ -264,13 +283,16 @@ void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* _
     const uint64_t per = ((uint64_t)n_blocks + 255) / 256;
     const uint64_t b0 = t * per < n_blocks ? t * per : n_blocks;
     const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+    const bool store = (flags & kFrameStored) != 0;
+    const uint64_t bb = 1ull << block_bits;
+    const uint64_t most_words = store ? 0x7FFFFFFFull : 0xFFFFFFFFull;     // bit 31 of the entry is the stored bit
     uint64_t sum = 0;
     int32_t bad = 0;
     for (uint64_t b = b0; b < b1; b++) {
         const uint64_t v = out_bytes[b];
         if (bad == 0 && err[b] != 0) { bad = err[b]; }
-        if (bad == 0 && ((v & 7u) != 0 || (v >> 3) > 0xFFFFFFFFull)) { bad = kErrEINVAL; }
-        sum += v;
+        if (bad == 0 && ((v & 7u) != 0 || (v >> 3) > most_words)) { bad = kErrEINVAL; }
+        sum += store ? payload_share(v, block_len(b, bb, content_bytes)) : v;
     }
     sums[t] = sum;
     first_err[t] = bad;
@@ -295,7 +317,8 @@ void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* _
         if (st == 0) {
             uint32_t* const h = reinterpret_cast<uint32_t*>(frame);
             h[0] = 0x465A5153u;                                    // "SQZF"
-            h[1] = 1u | (win_bits << 8) | (block_bits << 16);      // version, win_bits, block_bits, flags = 0
+            h[1] = (store ? 2u : 1u) | (win_bits << 8) | (block_bits << 16) | ((flags & 0xFFu) << 24);     // version,
+                                                                   // win_bits, block_bits, flags
             h[2] = (uint32_t)content_bytes; h[3] = (uint32_t)(content_bytes >> 32);
             h[4] = (uint32_t)run; h[5] = (uint32_t)(run >> 32);
             h[6] = n_blocks;
@@ -309,10 +332,14 @@ void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* _
     uint64_t at = payload_off + sums[t];
     for (uint64_t b = b0; b < b1; b++) {
         const uint64_t v = out_bytes[b];
+        const uint64_t len = block_len(b, bb, content_bytes);
+        const bool st = store && v >= len;
+        const uint64_t share = store ? payload_share(v, len) : v;
         dense_off[b] = ok ? at : 0;
-        copy_bytes[b] = ok ? v : 0;
-        if (ok) { index[2 * b] = (uint32_t)(v >> 3); index[2 * b + 1] = crc[b]; }
-        at += v;
+        copy_bytes[b] = ok && !st ? v : 0;
+        if (store) { stored[b] = ok && st ? 1u : 0u; }
+        if (ok) { index[2 * b] = (uint32_t)(share >> 3) | (st ? kStoredBit : 0u); index[2 * b + 1] = crc[b]; }
+        at += share;
     }
     if (b1 == n_blocks && (b0 < b1 || t == 0)) { dense_off[n_blocks] = ok ? at : 0; }
 }
@@ -323,7 +350,16 @@ void launch_frame_index(const uint64_t* out_bytes, const int32_t* err, const uin
                         uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream) {
     hipLaunchKernelGGL(frame_index_kernel, dim3(1), dim3(256), 0, stream, out_bytes, err, crc, n_blocks,
                        content_bytes, win_bits, block_bits, frame, capacity, copy_bytes, dense_off, idx_off,
-                       frame_bytes_out, status_out);
+                       frame_bytes_out, status_out, 0u, (uint32_t*)nullptr);
+}
+
+void launch_frame_index_v2(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
+                           uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint8_t* frame,
+                           uint64_t capacity, uint64_t* copy_bytes, uint64_t* dense_off, uint32_t* stored,
+                           uint64_t* idx_off, uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_index_kernel, dim3(1), dim3(256), 0, stream, out_bytes, err, crc, n_blocks,
+                       content_bytes, win_bits, block_bits, frame, capacity, copy_bytes, dense_off, idx_off,
+                       frame_bytes_out, status_out, kFrameStored, stored);
 }
 
 // index_crc = crc32(header[0, 28) || index): the header's 28 bytes on the spot, joined with the index's
@@ -350,12 +386,19 @@ void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_block
 // and that the payload lies inside avail.  Then in_off (absolute, from the start of the frame) and out_off
 // (from the start of block `first`) for blocks [first, first + n_sel).  On any failure *status is set and
 // every selected block gets a zero-length input and output: nothing behind the index is ever addressed.
+//
+// A version-2 frame (flags = SQZ_FRAME_STORED) needs `stored` (n_sel entries; EINVAL without it): bit 31 of an
+// entry's first word marks a stored block, the other 31 bits are its share of the payload in words, which for a
+// stored block must be ceil(length / 8) exactly (EINVAL, checked once index_crc has held).  stored[k] = 1 for a
+// selected stored block, 0 otherwise -- all zeros for a version-1 frame and on any refusal.
 __global__ __launch_bounds__(256)
 void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
                        uint64_t content_bytes, uint32_t first, uint32_t n_sel,
                        const uint32_t* __restrict__ idx_crc, uint64_t* __restrict__ in_off,
-                       uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out) {
+                       uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out,
+                       uint32_t* __restrict__ stored) {
     __shared__ uint64_t sums[256];
+    __shared__ uint32_t wrong[256];
     __shared__ int32_t verdict;
     __shared__ uint32_t want_crc;
     const uint32_t t = threadIdx.x;
@@ -369,23 +412,37 @@ void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32
     const uint64_t per = ((uint64_t)n_blocks + 255) / 256;
     const uint64_t b0 = t * per < n_blocks ? t * per : n_blocks;
     const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+    const uint32_t block_bits = frame[6];
+    const bool v2 = frame[4] == 2;
+    const uint32_t words_mask = v2 ? ~kStoredBit : 0xFFFFFFFFu;
     uint64_t sum = 0;
-    for (uint64_t b = b0; b < b1; b++) { sum += (uint64_t)index[2 * b] * 8; }
+    uint32_t misfit = 0;                           // a stored entry whose size is not its block's
+    for (uint64_t b = b0; b < b1; b++) {
+        const uint32_t e = index[2 * b];
+        if (v2 && (e & kStoredBit) != 0 && block_bits <= 24 &&
+            (uint64_t)(e & words_mask) != (block_len(b, 1ull << block_bits, content_bytes) + 7) / 8) { misfit = 1; }
+        sum += (uint64_t)(e & words_mask) * 8;
+    }
     sums[t] = sum;
+    wrong[t] = misfit;
     __syncthreads();
     const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + 15) & ~(uint64_t)15;
-    const uint32_t block_bits = frame[6];
     if (t == 0) {
         uint64_t run = 0;
         bool beyond = false;                       // the streams add up to more than there is: stop adding (no wrap)
+        uint32_t any_misfit = 0;
         for (int k = 0; k < 256; k++) {
             const uint64_t v = sums[k];            // < 2^59: at most 2^24 entries of less than 2^35 each
             sums[k] = run;
             if (v > avail || run > avail - v) { beyond = true; } else { run += v; }
+            any_misfit |= wrong[k];
         }
         int32_t st = 0;
         const uint32_t win_bits = frame[5];
-        if (load_le32(frame) != 0x465A5153u || frame[4] != 1 || frame[7] != 0 || win_bits < 10 || win_bits > 15 ||
+        // version 1 has no flags; version 2 has some, all of them known, and needs somewhere to put the mask
+        const bool version_ok = (frame[4] == 1 && frame[7] == 0) ||
+                                (frame[4] == 2 && frame[7] == kFrameStored && (stored != nullptr || n_sel == 0));
+        if (load_le32(frame) != 0x465A5153u || !version_ok || win_bits < 10 || win_bits > 15 ||
             block_bits < 12 || block_bits > 24) {
             st = kErrEINVAL;
         } else {
@@ -396,6 +453,8 @@ void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32
                 st = kErrEINVAL;
             } else if (load_le32(frame + 28) != want_crc) {
                 st = kErrEILSEQ;
+            } else if (any_misfit != 0) {
+                st = kErrEINVAL;
             } else if (!beyond && load_le64(frame + 16) != run) {
                 st = kErrEINVAL;
             } else if (beyond || payload_off > avail || run > avail - payload_off) {
@@ -407,15 +466,22 @@ void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32
     }
     __syncthreads();
     if (verdict != 0) {                            // refused: nothing below looks at the index again
-        for (uint64_t k = t; k <= n_sel; k += 256) { in_off[k] = 0; out_off[k] = 0; }
+        for (uint64_t k = t; k <= n_sel; k += 256) {
+            in_off[k] = 0; out_off[k] = 0;
+            if (stored != nullptr && k < n_sel) { stored[k] = 0; }
+        }
         return;
     }
     const uint64_t bb = 1ull << block_bits;
     const uint64_t base = (uint64_t)first * bb;
     uint64_t at = payload_off + sums[t];
     for (uint64_t b = b0; b < b1; b++) {
+        const uint32_t e = index[2 * b];
         if (b >= first && b <= (uint64_t)first + n_sel) { in_off[b - first] = at; }
-        at += (uint64_t)index[2 * b] * 8;
+        if (stored != nullptr && b >= first && b < (uint64_t)first + n_sel) {
+            stored[b - first] = v2 && (e & kStoredBit) != 0 ? 1u : 0u;
+        }
+        at += (uint64_t)(e & words_mask) * 8;
     }
     if (b1 == n_blocks && (b0 < b1 || t == 0) && (uint64_t)first + n_sel == n_blocks) { in_off[n_sel] = at; }
     for (uint64_t k = t; k <= n_sel; k += 256) {
@@ -428,7 +494,14 @@ void launch_frame_open(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, 
                        uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
                        uint64_t* out_off, int32_t* status_out, hipStream_t stream) {
     hipLaunchKernelGGL(frame_open_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
-                       first, n_sel, idx_crc, in_off, out_off, status_out);
+                       first, n_sel, idx_crc, in_off, out_off, status_out, (uint32_t*)nullptr);
+}
+
+void launch_frame_open_v2(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                          uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
+                          uint64_t* out_off, uint32_t* stored, int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_open_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
+                       first, n_sel, idx_crc, in_off, out_off, status_out, stored);
 }
 
 // err[k] for the selected blocks: the frame's status where it was refused; EILSEQ where the decoder was
@@ -450,6 +523,90 @@ void launch_frame_verify(const uint8_t* frame, uint32_t first, uint32_t n_sel, c
     if (n_sel == 0) { return; }
     hipLaunchKernelGGL(frame_verify_kernel, dim3((n_sel + 255) / 256), dim3(256), 0, stream,
                        frame, first, n_sel, crc, status, err);
+}
+
+// ---------------------------------------------------------------------------------------- stored blocks
+// Ragged range copy: range b is len_off[b + 1] - len_off[b] bytes from src + src_off[b] to dst + dst_off[b], for
+// the ranges whose mask[b] is non-zero (all of them with a null mask); with pad8 the destination is filled with
+// zeros up to the next multiple of 8 bytes of its length.  len_off is src_off (encode: content into the payload)
+// or dst_off (decode: payload into the output).  Nothing is assumed about alignment and nothing outside a range
+// is read or, padding aside, written: the destination is cut into 16-byte rows on ADDRESS boundaries, every full
+// row is one aligned 16-byte store, and its source bytes are one aligned 16-byte load when both sides share the
+// alignment, two aligned loads joined by a byte shift when they do not and both source rows lie inside the
+// range, single bytes otherwise (the first and last rows of a misaligned range).  `groups` workgroups share a
+// range row by row, so one 16 MB block fills the chip as 4096 blocks of 256 KB do.
+constexpr int kCopyThreads = 256;
+
+__device__ __forceinline__ uint64_t join_bytes(uint64_t lo, uint64_t hi, uint32_t s) {     // bytes s .. s + 7 of lo:hi
+    return s == 0 ? lo : (lo >> (8 * s)) | (hi << (64 - 8 * s));
+}
+
+__global__ __launch_bounds__(kCopyThreads)
+void range_copy_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
+                       uint8_t* __restrict__ dst, const uint64_t* __restrict__ dst_off,
+                       const uint64_t* __restrict__ len_off, const uint32_t* __restrict__ mask, uint32_t n_ranges,
+                       uint32_t pad8, uint32_t groups) {
+    const uint32_t b = blockIdx.x / groups, g = blockIdx.x % groups;
+    if (b >= n_ranges) { return; }
+    if (mask != nullptr && mask[b] == 0) { return; }
+    const uint64_t l0 = len_off[b], l1 = len_off[b + 1];
+    const uint64_t len = l1 > l0 ? l1 - l0 : 0;
+    const uint8_t* const from = src + src_off[b];
+    uint8_t* const to = dst + dst_off[b];
+    const uint32_t tid = threadIdx.x;
+    uint64_t head = (16u - (uint32_t)((uintptr_t)to & 15u)) & 15u;     // bytes in front of the first full row
+    if (head > len) { head = len; }
+    const uint64_t rows = (len - head) / 16;
+    const uint64_t tail_at = head + 16 * rows;                         // bytes behind the last full row
+    if (g == 0) {
+        if (tid < head) { to[tid] = from[tid]; }
+        if (tid >= 32 && tid - 32 < len - tail_at) { to[tail_at + (tid - 32)] = from[tail_at + (tid - 32)]; }
+        const uint64_t padded = (len + 7) & ~(uint64_t)7;
+        if (pad8 != 0 && tid >= 64 && len + (tid - 64) < padded) { to[len + (tid - 64)] = 0; }
+    }
+    const uint8_t* const fb = from + head;
+    uint8_t* const tb = to + head;                                     // 16-byte aligned
+    const uint32_t sh = (uint32_t)((uintptr_t)fb & 15u);               // where a row's bytes start in their source row
+    const uint8_t* const src_end = from + len;
+    for (uint64_t k = (uint64_t)g * kCopyThreads + tid; k < rows; k += (uint64_t)groups * kCopyThreads) {
+        const uint8_t* const sp = fb + 16 * k;
+        uint4 v;
+        if (sh == 0) {
+            v = *reinterpret_cast<const uint4*>(sp);
+        } else if (sp - sh >= from && sp - sh + 32 <= src_end) {
+            const uint4 a = *reinterpret_cast<const uint4*>(sp - sh);
+            const uint4 c = *reinterpret_cast<const uint4*>(sp - sh + 16);
+            const uint64_t q0 = (uint64_t)a.x | ((uint64_t)a.y << 32), q1 = (uint64_t)a.z | ((uint64_t)a.w << 32);
+            const uint64_t q2 = (uint64_t)c.x | ((uint64_t)c.y << 32), q3 = (uint64_t)c.z | ((uint64_t)c.w << 32);
+            const bool up = sh >= 8;
+            const uint32_t s = sh & 7u;
+            const uint64_t lo = join_bytes(up ? q1 : q0, up ? q2 : q1, s);
+            const uint64_t hi = join_bytes(up ? q2 : q1, up ? q3 : q2, s);
+            v.x = (uint32_t)lo; v.y = (uint32_t)(lo >> 32); v.z = (uint32_t)hi; v.w = (uint32_t)(hi >> 32);
+        } else {
+            uint32_t w[4] = {0u, 0u, 0u, 0u};       // a source row that is not whole inside the range: byte by byte
+#pragma unroll
+            for (uint32_t j = 0; j < 16; j++) { w[j >> 2] |= (uint32_t)sp[j] << (8 * (j & 3)); }
+            v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+        }
+        *reinterpret_cast<uint4*>(tb + 16 * k) = v;
+    }
+}
+
+void launch_range_copy(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, const uint64_t* dst_off,
+                       const uint64_t* len_off, const uint32_t* mask, uint32_t n_ranges, bool pad8,
+                       uint64_t size_hint, hipStream_t stream) {
+    if (n_ranges == 0) { return; }
+    // one workgroup per 32 KB of a range, about 8192 workgroups at the most; the workgroups of a range that is
+    // left out, or is shorter than the hint, leave at once
+    uint64_t groups = size_hint != 0 ? (size_hint + 32767) / 32768 : 512;
+    const uint64_t cap = 8192 / n_ranges > 1 ? 8192 / n_ranges : 1;
+    if (groups > cap) { groups = cap; }
+    if (groups > 2048) { groups = 2048; }
+    if (groups < 1) { groups = 1; }
+    while (groups > 1 && groups * n_ranges > 0x7FFFFFFFull) { groups /= 2; }
+    hipLaunchKernelGGL(range_copy_kernel, dim3((unsigned)(groups * n_ranges)), dim3(kCopyThreads), 0, stream,
+                       src, src_off, dst, dst_off, len_off, mask, n_ranges, pad8 ? 1u : 0u, (uint32_t)groups);
 }
 
 } // namespace sqzk

@@ -47,11 +47,15 @@ void launch_tree_debug(const int32_t* symbols, uint32_t count, int which, int ba
 
 // decode (squeeze.h:502-551): entropy stage -> token words -> LZ77 expansion.
 // tokens: one uint32 slot per OUTPUT byte, addressed by out_off; tok_count[n].
+// skip (optional, n_blocks entries): a block whose entry is non-zero is not a stream (an SQZF stored block): its
+// workgroup leaves at once with err = 0 and tok_count = 0, and the expansion does not touch its output.
 void launch_entropy_decode(const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off,
                            uint32_t* tokens, uint32_t* tok_count, int32_t* err, uint64_t* end_bit,
-                           uint32_t n_blocks, uint64_t start_bit, int waves, hipStream_t stream);
+                           uint32_t n_blocks, uint64_t start_bit, int waves, hipStream_t stream,
+                           const uint32_t* skip = nullptr);
 void launch_lz_expand(const uint32_t* tokens, const uint32_t* tok_count, uint8_t* out,
-                      const uint64_t* out_off, uint32_t n_blocks, hipStream_t stream);
+                      const uint64_t* out_off, uint32_t n_blocks, hipStream_t stream,
+                      const uint32_t* skip = nullptr);
 
 // the reference's HEAD range coder (range_coder.hip): literal-only encode as HEAD
 // runs it, decode as written.  Block b: in[in_off[b] .. in_off[b+1]) -> out + out_off[b], at most
@@ -88,6 +92,22 @@ void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_block
 void launch_frame_open(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
                        uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
                        uint64_t* out_off, int32_t* status_out, hipStream_t stream);
+// version 2 (SQZ_FRAME_STORED): the same kernels deciding / reading which blocks are stored.  index: stored[n]
+// marks them and copy_bytes[] is 0 for them; open: stored[n_sel] is the mask for the decode kernels' `skip`
+// and for launch_range_copy (all zeros for a version-1 frame, which this launcher takes as well)
+void launch_frame_index_v2(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
+                           uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint8_t* frame,
+                           uint64_t capacity, uint64_t* copy_bytes, uint64_t* dense_off, uint32_t* stored,
+                           uint64_t* idx_off, uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream);
+void launch_frame_open_v2(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                          uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
+                          uint64_t* out_off, uint32_t* stored, int32_t* status_out, hipStream_t stream);
+// ragged copy: len_off[b+1] - len_off[b] bytes from src + src_off[b] to dst + dst_off[b] where mask[b] != 0
+// (null: everywhere), any alignment; pad8: zeros up to the next multiple of 8 behind each range.  size_hint
+// as for launch_crc32_blocks
+void launch_range_copy(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, const uint64_t* dst_off,
+                       const uint64_t* len_off, const uint32_t* mask, uint32_t n_ranges, bool pad8,
+                       uint64_t size_hint, hipStream_t stream);
 void launch_frame_verify(const uint8_t* frame, uint32_t first, uint32_t n_sel, const uint32_t* crc,
                          const int32_t* status, int32_t* err, hipStream_t stream);
 

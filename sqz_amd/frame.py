@@ -3,9 +3,12 @@
 Host flavour (bytes in, bytes out) and a device flavour over torch tensors in the style of batch.py.
 Every byte of codec and checksum work happens in libsqz_amd.so; nothing is computed here.
 
-    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18]     compress a file
+    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18] [--store]    compress a file
     python -m sqz_amd.frame d IN OUT                                       decompress one
     python -m sqz_amd.frame info IN                                        describe one
+    python -m sqz_amd.frame blocks IN                                      one line per block
+
+store=True / --store writes version 2: a block whose stream is not smaller than its content is stored as it is.
 """
 import ctypes as C
 import errno
@@ -14,11 +17,16 @@ from . import _native as N
 from .codec import SqzError, _raise
 
 HEADER_BYTES = 32
+FRAME_STORED = 1            # SQZ_FRAME_STORED
 
 
-def frame_bound(nbytes: int, block_bits: int = 18) -> int:
+def _flags(store: bool) -> int:
+    return FRAME_STORED if store else 0
+
+
+def frame_bound(nbytes: int, block_bits: int = 18, store: bool = False) -> int:
     """worst-case size of the frame of `nbytes` bytes of content"""
-    return int(N.lib().sqz_frame_bound(nbytes, block_bits))
+    return int(N.lib().sqz_frame_bound_ex(nbytes, block_bits, _flags(store)))
 
 
 def frame_info(frame) -> dict:
@@ -30,16 +38,26 @@ def frame_info(frame) -> dict:
     return {k: int(getattr(fi, k)) for k, _ in N.FrameInfo._fields_ if k != "reserved"}
 
 
-def compress_frame(data, win_bits: int = 15, block_bits: int = 18) -> bytes:
+def frame_blocks(frame) -> list:
+    """One dict per block (sqz_frame_blocks): payload_off (from the start of the frame), payload_bytes,
+    content_bytes, content_crc, stored.  Host code: needs header and index, no device is touched."""
+    frame = bytes(frame)
+    n = frame_info(frame)["n_blocks"]
+    out = (N.FrameBlock * max(n, 1))()
+    _raise(N.lib().sqz_frame_blocks(frame, len(frame), 0, n, out), "sqz_frame_blocks")
+    return [{k: int(getattr(out[b], k)) for k, _ in N.FrameBlock._fields_} for b in range(n)]
+
+
+def compress_frame(data, win_bits: int = 15, block_bits: int = 18, store: bool = False) -> bytes:
     data = bytes(data)
-    cap = frame_bound(len(data), block_bits)
+    cap = frame_bound(len(data), block_bits, store)
     if cap == 0:
         raise SqzError(errno.EINVAL, "sqz_frame_compress: block_bits out of range")
     out = bytearray(cap)
     n = C.c_uint64(0)
     dst = (C.c_uint8 * cap).from_buffer(out)
-    _raise(N.lib().sqz_frame_compress(data, len(data), win_bits, block_bits, dst, cap, C.byref(n)),
-           "sqz_frame_compress")
+    _raise(N.lib().sqz_frame_compress_ex(data, len(data), win_bits, block_bits, _flags(store), dst, cap, C.byref(n)),
+           "sqz_frame_compress_ex")
     del dst
     return bytes(out[:n.value])
 
@@ -103,34 +121,35 @@ class FrameEncoder:
     encode() enqueues and returns; frame_bytes / status / err are device tensors to read after a synchronise."""
 
     def __init__(self, content_bytes: int, win_bits: int = 15, block_bits: int = 18, capacity: int = None,
-                 device="cuda"):
+                 device="cuda", store: bool = False):
         import torch
         L = N.lib()
         self.win_bits, self.block_bits, self.content_bytes = win_bits, block_bits, content_bytes
-        self.capacity = frame_bound(content_bytes, block_bits) if capacity is None else capacity
+        self.flags = _flags(store)
+        self.capacity = frame_bound(content_bytes, block_bits, store) if capacity is None else capacity
         self.n_blocks = (content_bytes + (1 << block_bits) - 1) >> block_bits
         self.frame = torch.empty(max(self.capacity, 16), dtype=torch.uint8, device=device)
         self.frame_bytes = torch.zeros(1, dtype=torch.int64, device=device)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
         self.err = torch.zeros(max(self.n_blocks, 1), dtype=torch.int32, device=device)
-        self.scratch_bytes = int(L.sqz_hip_frame_scratch_bytes(content_bytes, block_bits, 1))
+        self.scratch_bytes = int(L.sqz_hip_frame_scratch_bytes_ex(content_bytes, block_bits, 1, self.flags))
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=device)
 
     def encode(self, d_in, content_bytes: int = None):
         nbytes = d_in.numel() if content_bytes is None else content_bytes
         if nbytes > self.content_bytes:
             raise SqzError(errno.E2BIG, "FrameEncoder: more content than the buffers were made for")
-        _raise(N.lib().sqz_hip_frame_encode(
-            _ptr(d_in), nbytes, self.win_bits, self.block_bits, _ptr(self.frame), self.capacity,
+        _raise(N.lib().sqz_hip_frame_encode_ex(
+            _ptr(d_in), nbytes, self.win_bits, self.block_bits, self.flags, _ptr(self.frame), self.capacity,
             _ptr(self.frame_bytes), _ptr(self.status), _ptr(self.err), _ptr(self.scratch), self.scratch_bytes,
-            _stream()), "sqz_hip_frame_encode")
+            _stream()), "sqz_hip_frame_encode_ex")
         return self.frame, self.frame_bytes, self.status, self.err
 
     def result(self) -> bytes:
         """synchronise and fetch the frame of the last encode(); raises on a frame-level status"""
         import torch
         torch.cuda.synchronize()
-        _raise(int(self.status.item()), "sqz_hip_frame_encode (status)")
+        _raise(int(self.status.item()), "sqz_hip_frame_encode_ex (status)")
         return self.frame[:int(self.frame_bytes.item())].cpu().numpy().tobytes()
 
 
@@ -173,19 +192,26 @@ def main(argv=None) -> int:
     c.add_argument("dst")
     c.add_argument("--win-bits", type=int, default=15)
     c.add_argument("--block-bits", type=int, default=18)
+    c.add_argument("--store", action="store_true", help="version 2: store a block whose stream is not smaller")
     d = sub.add_parser("d", help="decompress IN to OUT")
     d.add_argument("src")
     d.add_argument("dst")
     i = sub.add_parser("info", help="describe IN")
     i.add_argument("src")
+    k = sub.add_parser("blocks", help="one line per block of IN")
+    k.add_argument("src")
     a = ap.parse_args(argv)
     with open(a.src, "rb") as fh:
         blob = fh.read()
     try:
         if a.cmd == "c":
-            out = compress_frame(blob, a.win_bits, a.block_bits)
+            out = compress_frame(blob, a.win_bits, a.block_bits, a.store)
         elif a.cmd == "d":
             out = decompress_frame(blob)
+        elif a.cmd == "blocks":
+            for b, blk in enumerate(frame_blocks(blob)):
+                print(f"{b}: " + " ".join(f"{key}={v}" for key, v in blk.items()))
+            return 0
         else:
             for k, v in frame_info(blob).items():
                 print(f"{k}: {v}")
