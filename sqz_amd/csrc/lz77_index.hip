@@ -633,6 +633,11 @@ void index_match_kernel(const uint8_t* __restrict__ in,
 // where the previous chunk's path left -- only has to be followed until it steps on a
 // position the guess also visited; from there the guess is right.  That fix-up runs chunk
 // by chunk, a few hops each, instead of one hop per token.
+//
+// No memory round trip stands in a tile's way: its 32 rows of match words are loaded back to back
+// into registers while the tile before is walked, and its token words, packed in LDS, leave in 32
+// stores of 64 consecutive words that nothing waits for.  (One load, one wait, one LDS write, 32
+// times per tile, behind the lane-strided token stores of the tile before, was 60 % of the kernel.)
 constexpr int kChunk = 32;                          // positions per lane (<= 32: one mask bit each)
 constexpr int kTile = kChunk * kWave;               // positions per pass
 constexpr int kChunkRow = kChunk + 1;               // padded: same-offset reads of all lanes spread over the banks
@@ -640,9 +645,11 @@ constexpr int kChunkRow = kChunk + 1;               // padded: same-offset reads
 // 8,448 B per stream: 16 streams per CU, the whole 4096-block batch in one round (with the tile's
 // bytes staged as well it was 10,496 B, 15 per CU and two rounds: 9.9 ms instead of 5).  The
 // literal travels in the match word instead: len << 16 | dist for a match (len >= 3), the byte
-// itself (len field 0) where index_match_kernel found none.
+// itself (len field 0) where index_match_kernel found none.  Once every lane has taken its chunk's
+// words into registers the same words hold the tile's token words, token n at m[n] (unpadded), on
+// their way out.
 struct ParseLds {
-    uint32_t m[kChunkRow * kWave];                  // match word per position
+    uint32_t m[kChunkRow * kWave];                  // match word per position (row l = chunk l, padded); then the tile's token words
 };
 
 __device__ __forceinline__ uint32_t parse_slot(uint32_t k) { return k + (k / (uint32_t)kChunk); }
@@ -655,6 +662,49 @@ __device__ __forceinline__ uint32_t parse_step(uint32_t w) {
     return len != 0 ? len : 1u;
 }
 
+// A tile's match words as they travel: lane l holds positions l, l + 64, ... of the tile, one coalesced load each,
+// all issued back to back.  Positions past the stream's end read its last word again (clamped, never used).
+constexpr int kTileRows = kTile / kWave;
+__device__ __forceinline__ void parse_fetch(uint32_t (&w)[kTileRows], const uint32_t* __restrict__ M,
+                                            const uint64_t tile, const uint64_t bytes, const int lane) {
+    const uint64_t left = bytes - tile;
+    const uint32_t last = left < (uint64_t)kTile ? (uint32_t)left - 1u : (uint32_t)kTile - 1u;
+    const uint32_t* __restrict__ T = M + tile;
+#pragma unroll
+    for (int j = 0; j < kTileRows; j++) {
+        const uint32_t k = (uint32_t)(j * kWave + lane);
+        w[j] = T[k < last ? k : last];
+    }
+}
+
+// A value the compiler must work out again in every tile: without it the lane's 32 slot numbers of an unrolled
+// loop are kept in 32 registers across the tiles, and the kernel no longer fits 4 waves per SIMD.
+__device__ __forceinline__ uint32_t per_tile(uint32_t v) {
+#ifndef SQZ_WAVE_EMU
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+
+// Section timers of the instrumented build (tools/build_stats.sh): cycles of block 1 per section, summed over its
+// tiles.  0 the tile's words have arrived (the instrumented build waits for them there: vmcnt(0), which also waits
+// for the token stores of the tile before), 1 stage to LDS and send for the next tile, 2 guess walk, 3 fix-up
+// across the 64 chunks, 4 token write (pack in LDS, issue the stores).
+struct ParseSec {
+#ifdef SQZ_STATS
+    uint64_t t[5] = {0, 0, 0, 0, 0};
+    uint64_t last = 0;
+#endif
+};
+#ifdef SQZ_STATS
+#define PARSE_SEC(s, k) SORT_SEC(s, k)
+#define PARSE_SEC_LOADS(s, k) SORT_SEC_LOADS(s, k)
+#else
+#define PARSE_SEC(s, k)
+#define PARSE_SEC_LOADS(s, k)
+#endif
+
+// 117 VGPRs (a tile in flight, a chunk's words): the 4 waves per SIMD = 16 streams per CU that the LDS admits need <= 128
 __global__ __launch_bounds__(kWave)
 void index_parse_kernel(const uint8_t* __restrict__ in,
                         const uint64_t* __restrict__ in_off,
@@ -675,18 +725,42 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
     const uint32_t* M = match + in_off[b];
     uint32_t* tok = tokens + in_off[b];
 
+    if (bytes == 0) {
+        if (lane == 0) { tok_count[b] = 0; }
+        return;
+    }
+    // positions bytes-2, bytes-1 have no 3-byte prefix and no match word: literals
+    const uint32_t lit1 = (uint32_t)src[bytes - 1];
+    const uint32_t lit2 = (uint32_t)src[bytes >= 2 ? bytes - 2 : 0];
+
+    ParseSec sec;
+#ifdef SQZ_STATS
+    sec.last = __builtin_readcyclecounter();
+    const uint64_t sec_begin = sec.last;
+#endif
     uint32_t ntok = 0;
     uint32_t entry = 0;                              // where the real path enters the tile (tile-relative)
-    for (uint64_t tile = 0; tile < bytes; tile += (uint64_t)kTile) {
+    uint32_t fly[kTileRows];                         // the tile in flight
+    parse_fetch(fly, M, 0, bytes, lane);
+    // one tile; false: the path has left the stream (its last token reaches over the ragged last tile)
+    auto do_tile = [&](const uint64_t tile) __attribute__((always_inline)) -> bool {
         const uint64_t left = bytes - tile;
         const uint32_t have = left < (uint64_t)kTile ? (uint32_t)left : (uint32_t)kTile;
-        if (entry >= have) { entry -= (uint32_t)kTile; continue; }         // a token spans the whole tile
-        __syncthreads();
-        for (uint32_t k = lane; k < have; k += kWave) {
-            // positions bytes-2, bytes-1 have no 3-byte prefix: literal
-            lds.m[parse_slot(k)] = (tile + k + 2 < bytes) ? M[tile + k] : (uint32_t)src[tile + k];
+        if (entry >= have) { return false; }
+        PARSE_SEC_LOADS(sec, 0)
+        lds_barrier();                               // the tile before has been copied out of lds.m
+        const int t2 = left < (uint64_t)(kTile + 2) ? (int)left - 2 : kTile;     // tile-relative: position bytes-2
+        uint32_t* const mine_at = &lds.m[parse_slot((uint32_t)lane)];
+#pragma unroll
+        for (int j = 0; j < kTileRows; j++) {        // position j * kWave + lane: a row of 64 lies 64 + 64 / kChunk slots behind the row before
+            const int tj = t2 - j * kWave;
+            mine_at[j * (kWave + kWave / kChunk)] = lane < tj ? fly[j] : lane == tj ? lit2 : lit1;
         }
-        __syncthreads();
+        lds_barrier();
+        // the next tile's words set out now and are taken up after this tile's tokens have left (behind the
+        // last tile: the same tile once more, into registers nobody reads)
+        parse_fetch(fly, M, tile + (uint64_t)kTile < bytes ? tile + (uint64_t)kTile : tile, bytes, lane);
+        PARSE_SEC(sec, 1)
 
         // ---- every lane: its chunk from the chunk's first position ---------------------
         const uint32_t lo = (uint32_t)lane * (uint32_t)kChunk;
@@ -700,49 +774,93 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
             p += parse_step(w);
         }
         const uint32_t guess_out = lo + p;           // where the guess leaves the chunk (>= lo + room)
+        PARSE_SEC(sec, 2)
 
         // ---- the real path, chunk by chunk (uniform) -----------------------------------
-        uint32_t mine = 0;                           // this lane's chunk: real token starts
+        // One turn per chunk the path enters (a long token takes it straight to the chunk it lands in).  Where
+        // the path enters on a position the guess visited -- most chunks -- the turn is two lane reads and a
+        // handful of scalar instructions; otherwise it hops through LDS until it meets the guess or leaves the
+        // chunk.  A lane only notes where its chunk's real path meets its guess (`from`) and the token starts in
+        // front of that (`extra`); the bitmaps are put together by all lanes at once afterwards.
+        uint32_t extra = 0;
+        uint32_t from = (uint32_t)kChunk;            // kChunk: the path never meets this lane's guess
         uint32_t e = entry;
-        for (int l = 0; l < kWave; l++) {
-            const uint32_t clo = (uint32_t)l * (uint32_t)kChunk;
-            if (clo >= have) { break; }
-            const uint32_t chi = clo + (uint32_t)kChunk < have ? clo + (uint32_t)kChunk : have;
-            if (e >= chi) { continue; }              // the path jumps over this chunk
-            const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)guess, l);
-            const uint32_t gout = (uint32_t)__builtin_amdgcn_readlane((int)guess_out, l);
-            uint32_t real = 0;
+        while (e < have) {
+            const uint32_t l = e / (uint32_t)kChunk;
+            const uint32_t clo = l * (uint32_t)kChunk;
+            const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)guess, (int)l);
             uint32_t q = e - clo;
-            const uint32_t croom = chi - clo;
-            for (;;) {
-                if ((g >> q) & 1u) {                 // the guess was here too: the rest is the guess's
-                    real |= g & ~((1u << q) - 1u);
-                    e = gout;
-                    break;
-                }
-                real |= 1u << q;
-                const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds.m[l * kChunkRow + (int)q]);
-                q += parse_step(w);
-                if (q >= croom) { e = clo + q; break; }
+            if (((g >> q) & 1u) != 0) {              // the guess was here too: the rest of the chunk is the guess's
+                e = (uint32_t)__builtin_amdgcn_readlane((int)guess_out, (int)l);
+                if ((uint32_t)lane == l) { from = q; }
+                continue;
             }
-            if (lane == l) { mine = real; }
+            const uint32_t croom = have - clo < (uint32_t)kChunk ? have - clo : (uint32_t)kChunk;
+            uint32_t real = 0;
+            do {                                     // it was not: hop
+                real |= 1u << q;
+                const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds.m[l * kChunkRow + q]);
+                q += parse_step(w);
+            } while (q < croom && ((g >> q) & 1u) == 0);
+            const bool met = q < croom;              // on a position of the guess (which has none at or beyond croom)
+            e = met ? (uint32_t)__builtin_amdgcn_readlane((int)guess_out, (int)l) : clo + q;
+            if ((uint32_t)lane == l) { extra = real; from = met ? q : (uint32_t)kChunk; }
         }
+        const uint32_t mine = extra | (from < (uint32_t)kChunk ? guess & (~0u << from) : 0u);   // this lane's chunk: real token starts
         entry = e - (uint32_t)kTile;                 // e >= have here; carried into the next tile
+        PARSE_SEC(sec, 3)
 
         // ---- token words, in order ----------------------------------------------------
+        // Every lane takes its chunk's words into registers; from then on the tile's match words are dead, and
+        // the token words are packed into the same LDS, token n of the tile at word n (no padding).  They leave
+        // 64 consecutive words per store, always kTileRows stores: the ones past the tile's last token write
+        // that last token again.  A fixed number of stores lets the wait for the next tile's words, which set
+        // out before them, count the stores off instead of waiting for them.
+        uint32_t mw[kChunk];
+#pragma unroll
+        for (int j = 0; j < kChunk; j++) { mw[j] = row[j]; }
         const uint32_t cnt = (uint32_t)__builtin_popcount(mine);
         const uint32_t incl = wave_scan(cnt);
-        uint32_t at = ntok + incl - cnt;
-        uint32_t bits = mine;
-        while (bits != 0) {
-            const uint32_t k = (uint32_t)__builtin_ctz(bits);
-            bits &= bits - 1u;
-            const uint32_t w = row[k];
-            tok[at++] = (w >> 16) != 0 ? (kTokMatch | w) : (w & 0xFFu);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1);   // >= 1: entry < have
+        lds_barrier();
+        uint32_t at = incl - cnt;
+#pragma unroll
+        for (int j = 0; j < kChunk; j++) {
+            if ((mine >> j) & 1u) {
+                lds.m[at++] = (mw[j] >> 16) != 0 ? (kTokMatch | mw[j]) : (mw[j] & 0xFFu);
+            }
         }
-        ntok += (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1);
+        lds_barrier();
+        uint32_t* const out = tok + ntok;
+        const uint32_t last = total - 1u;
+        const uint32_t ln = per_tile((uint32_t)lane);
+#pragma unroll
+        for (int j = 0; j < kTileRows; j++) {
+            const uint32_t k = (uint32_t)(j * kWave) + ln;
+            const uint32_t n = (k < last ? k : last) & (uint32_t)(kTile - 1);      // (the mask: a 32-bit offset for the store)
+            out[n] = lds.m[n];
+        }
+        ntok += total;
+        PARSE_SEC(sec, 4)
+        return true;
+    };
+    // The first tile stands apart from the loop: in the loop a tile's words are always kTileRows loads followed
+    // by kTileRows stores away, and the compiler's s_waitcnt vmcnt counts exactly that; merged with the way in
+    // from the first fetch (no stores behind it) it would have to wait for the stores as well.
+    static_assert(kTile > kLenMax, "a token never reaches over a whole tile");
+    if (do_tile(0)) {
+        for (uint64_t tile = (uint64_t)kTile; tile < bytes; tile += (uint64_t)kTile) {
+            if (!do_tile(tile)) { break; }
+        }
     }
     if (lane == 0) { tok_count[b] = ntok; }
+#ifdef SQZ_STATS
+    if (lane == 0 && b == 1) {
+        printf("parse block 1: cycles %llu: tiles: arrived %llu stage %llu guess %llu fixup %llu write %llu\n",
+               (unsigned long long)(sec.last - sec_begin), (unsigned long long)sec.t[0], (unsigned long long)sec.t[1],
+               (unsigned long long)sec.t[2], (unsigned long long)sec.t[3], (unsigned long long)sec.t[4]);
+    }
+#endif
 }
 
 void launch_index_sort(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
