@@ -469,6 +469,41 @@ SQZ_API int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uin
 SQZ_API void sqz_hip_set_finder(int finder);
 SQZ_API int  sqz_hip_get_finder(void);
 
+/* The parse as a per-call argument.  SQZ_PARSE_GREEDY is the reference's step (squeeze.h:377-394): through a
+ * _parse call it is the call without the suffix, the same kernels and the same bytes.  SQZ_PARSE_LAZY looks one
+ * position ahead: with L(i) the longest match at i (the finder's: strict >, nearest first, 0 or 3..257),
+ *     L(i) >= 3, i + 1 < n and L(i + 1) > L(i)   ->  the literal data[i], on to i + 1
+ *     otherwise L(i) >= 3                         ->  the match at i, on to i + L(i)
+ *     otherwise                                   ->  the literal data[i], on to i + 1
+ * No thresholds; one position after the other may give way.  The streams are NOT the reference's streams, but
+ * they are streams of the same format: every decoder here and the reference's own read them.  2-4 % smaller on
+ * text and executables, now and then larger (0.6 % on a bitmap): opt-in.  The lazy parse reads the match table
+ * and therefore always runs the indexed finder, whatever sqz_hip_set_finder / SQZ_FINDER say;
+ * sqz_hip_lz77_blocks_parse with finder 0 and SQZ_PARSE_LAZY is EINVAL.  Any other parse value is EINVAL at the
+ * call: nothing is launched, nothing written.  Every call is its counterpart plus `parse`: same arguments, same
+ * scratch sizes, same errors (ENODEV without a device).  The parse is not recorded in a frame: a lazy frame is an
+ * ordinary version-1 frame, or version 2 with SQZ_FRAME_STORED, whose rule then looks at the lazy stream's size. */
+#define SQZ_PARSE_GREEDY 0u
+#define SQZ_PARSE_LAZY 1u
+SQZ_API int sqz_encode_blocks_parse(const uint8_t* in, const uint64_t* in_off, uint32_t n, uint32_t window,
+                                    uint32_t parse, uint8_t* out, const uint64_t* out_off,
+                                    uint64_t* out_bytes, int32_t* err);
+SQZ_API int sqz_hip_encode_blocks_parse(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window,
+                                        uint32_t parse, void* d_out, const uint64_t* d_out_off,
+                                        uint64_t* d_out_bytes, int32_t* d_err,
+                                        void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API int sqz_hip_lz77_blocks_parse(const void* d_in, const uint64_t* d_in_off, uint32_t n,
+                                      uint32_t window, uint32_t* d_tokens,
+                                      uint32_t* d_token_count, int finder, uint32_t parse,
+                                      void* d_work, uint64_t work_bytes, void* stream);
+SQZ_API int sqz_frame_compress_parse(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                                     uint32_t flags, uint32_t parse, uint8_t* frame, uint64_t capacity,
+                                     uint64_t* frame_bytes);
+SQZ_API int sqz_hip_frame_encode_parse(const void* d_in, uint64_t content_bytes, uint32_t win_bits,
+                                       uint32_t block_bits, uint32_t flags, uint32_t parse, void* d_frame,
+                                       uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
+                                       int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* Live timing of the last kernels enqueued through this library on the
  * calling thread's context, measured with HIP events ON THE LAUNCH STREAM.
  * Enabled with sqz_hip_set_timing(1); values in milliseconds.               */

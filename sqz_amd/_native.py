@@ -143,6 +143,15 @@ PROTOTYPES = {
     "sqz_hip_frame_decode": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64,
                                        _vp]),
     "sqz_hip_crc32_blocks": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
+    "sqz_encode_blocks_parse": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "sqz_hip_encode_blocks_parse": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp,
+                                              _vp, C.c_uint64, _vp]),
+    "sqz_hip_lz77_blocks_parse": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_int, C.c_uint32, _vp,
+                                            C.c_uint64, _vp]),
+    "sqz_frame_compress_parse": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                           C.c_uint64, _u64p]),
+    "sqz_hip_frame_encode_parse": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                             C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
     "sqz_hip_set_finder": (None, [C.c_int]),
     "sqz_hip_get_finder": (C.c_int, []),
     "sqz_hip_set_timing": (None, [C.c_int]),

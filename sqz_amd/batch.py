@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .codec import SqzError, _raise
+from .codec import PARSE_LAZY, SqzError, _raise, parse_code
 
 
 def _ptr(t):
@@ -49,7 +49,14 @@ class Encoder:
         self.scratch_bytes = int(L.sqz_hip_encode_scratch_bytes(n_blocks, total_bytes))
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=device)
 
-    def encode(self, d_in, in_off, window: int):
+    def encode(self, d_in, in_off, window: int, parse: str = "greedy"):
+        """parse: "greedy" = the reference's streams, "lazy" = smaller ones of the same format (codec.parse_code)"""
+        if parse_code(parse) == PARSE_LAZY:
+            _raise(N.lib().sqz_hip_encode_blocks_parse(
+                _ptr(d_in), _ptr(in_off), self.n, window, PARSE_LAZY, _ptr(self.out), _ptr(self.out_off),
+                _ptr(self.out_bytes), _ptr(self.err), _ptr(self.scratch), self.scratch_bytes,
+                _stream()), "sqz_hip_encode_blocks_parse")
+            return self.out, self.out_off, self.out_bytes, self.err
         _raise(N.lib().sqz_hip_encode_blocks(
             _ptr(d_in), _ptr(in_off), self.n, window, _ptr(self.out), _ptr(self.out_off),
             _ptr(self.out_bytes), _ptr(self.err), _ptr(self.scratch), self.scratch_bytes,
@@ -75,11 +82,15 @@ class Encoder:
             res.append(d)
         return self.out, self.out_off, self.out_bytes, self.err, res
 
-    def tokens(self, d_in, in_off, window: int, finder: str = "index"):
+    def tokens(self, d_in, in_off, window: int, finder: str = "index", parse: str = "greedy"):
         """stage 1 alone: (tokens int32[total], counts int32[n]).
 
         finder: "scan" = brute force as the reference writes it, "index" = same
-        tokens through the sorted 3-byte-prefix index."""
+        tokens through the sorted 3-byte-prefix index.
+        parse: "greedy" or "lazy"; the lazy parse reads the index's match table, so it goes with "index" only."""
+        lazy = parse_code(parse) == PARSE_LAZY
+        if lazy and finder == "scan":
+            raise ValueError('parse="lazy" needs finder="index": the scan has no match table')
         total = int(in_off[-1].item())
         toks = torch.zeros(total + 64, dtype=torch.int32, device=self.device)
         counts = torch.zeros(self.n, dtype=torch.int32, device=self.device)
@@ -87,6 +98,13 @@ class Encoder:
             _raise(N.lib().sqz_hip_lz77_blocks(_ptr(d_in), _ptr(in_off), self.n, window,
                                                 _ptr(toks), _ptr(counts), _stream()),
                    "sqz_hip_lz77_blocks")
+        elif lazy:
+            work = torch.empty(8 * (total + 64), dtype=torch.uint8, device=self.device)
+            _raise(N.lib().sqz_hip_lz77_blocks_parse(_ptr(d_in), _ptr(in_off), self.n, window,
+                                                      _ptr(toks), _ptr(counts), 1, PARSE_LAZY, _ptr(work),
+                                                      work.numel(), _stream()),
+                   "sqz_hip_lz77_blocks_parse")
+            torch.cuda.synchronize()
         else:
             work = torch.empty(8 * (total + 64), dtype=torch.uint8, device=self.device)
             _raise(N.lib().sqz_hip_lz77_blocks_ex(_ptr(d_in), _ptr(in_off), self.n, window,
@@ -151,8 +169,9 @@ def get_timing(reset=True):
 
 
 # ---- host-buffer flavour (numpy in / numpy out) ------------------------------
-def encode_blocks_host(blocks, window: int, capacity=None):
-    """blocks: list of bytes-like.  Returns (list of compressed bytes, err array)."""
+def encode_blocks_host(blocks, window: int, capacity=None, parse: str = "greedy"):
+    """blocks: list of bytes-like.  Returns (list of compressed bytes, err array).  parse: codec.parse_code."""
+    lazy = parse_code(parse) == PARSE_LAZY
     L = N.lib()
     n = len(blocks)
     sizes = [len(b) for b in blocks]
@@ -166,8 +185,12 @@ def encode_blocks_host(blocks, window: int, capacity=None):
     out_bytes = np.zeros(n, np.uint64)
     err = np.zeros(n, np.int32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    _raise(L.sqz_encode_blocks(p(data), p(in_off), n, window, p(out), p(out_off), p(out_bytes),
-                               p(err)), "sqz_encode_blocks")
+    if lazy:
+        _raise(L.sqz_encode_blocks_parse(p(data), p(in_off), n, window, PARSE_LAZY, p(out), p(out_off), p(out_bytes),
+                                         p(err)), "sqz_encode_blocks_parse")
+    else:
+        _raise(L.sqz_encode_blocks(p(data), p(in_off), n, window, p(out), p(out_off), p(out_bytes),
+                                   p(err)), "sqz_encode_blocks")
     res = [out[int(out_off[b]):int(out_off[b]) + int(out_bytes[b])].tobytes() for b in range(n)]
     return res, err
 

@@ -19,6 +19,19 @@ class SqzError(OSError):
     pass
 
 
+PARSE_GREEDY, PARSE_LAZY = 0, 1     # SQZ_PARSE_GREEDY, SQZ_PARSE_LAZY
+
+
+def parse_code(parse: str) -> int:
+    """"greedy" (the reference's step, the default everywhere) or "lazy" (one position of look-ahead: smaller
+    streams of the same format, not the reference's bytes; always the indexed finder)"""
+    if parse == "greedy":
+        return PARSE_GREEDY
+    if parse == "lazy":
+        return PARSE_LAZY
+    raise ValueError(f'parse must be "greedy" or "lazy", not {parse!r}')
+
+
 def _raise(code, what):
     if code != 0:
         raise SqzError(code, f"{what}: {errno.errorcode.get(code, code)}")

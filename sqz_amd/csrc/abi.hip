@@ -311,11 +311,16 @@ uint32_t match_groups_for(uint64_t avg_block_bytes) {
     return (uint32_t)g;
 }
 
+bool parse_ok(uint32_t parse) { return parse == SQZ_PARSE_GREEDY || parse == SQZ_PARSE_LAZY; }
+// the lazy parse reads the match table, which only the indexed finder writes: it runs that finder whatever is set
+int finder_for(uint32_t parse) { return parse == SQZ_PARSE_LAZY ? 1 : finder_default(); }
+
 // stage 1 on device buffers -> token words; work = 2 arrays of one uint32 slot per input byte
+// (parse = SQZ_PARSE_LAZY: finder 1 and both work arrays, the callers see to that)
 void run_stage1(int finder, const uint8_t* d_in, const uint64_t* d_in_off, uint32_t n,
                 uint32_t window, uint32_t* tokens, uint32_t* counts,
                 uint32_t* work_a, uint32_t* work_m, uint64_t avg_block, uint64_t slots,
-                hipStream_t st) {
+                hipStream_t st, uint32_t parse = SQZ_PARSE_GREEDY) {
     if (finder == 0 || work_a == nullptr || work_m == nullptr) {
         SpanGuard g(st, SQZ_HIP_K_LZ77_SCAN);
         sqzk::launch_lz77_scan(d_in, d_in_off, n, window, tokens, counts, scan_waves(), slots, st);
@@ -329,7 +334,11 @@ void run_stage1(int finder, const uint8_t* d_in, const uint64_t* d_in_off, uint3
           sqzk::launch_index_match(d_in, d_in_off, n, window, work_a, work_m,
                                    match_groups_for(avg_block), slots, st); }
         { SpanGuard g(st, SQZ_HIP_K_INDEX_PARSE);
-          sqzk::launch_index_parse(d_in, d_in_off, n, work_m, tokens, counts, slots, st); }
+          if (parse == SQZ_PARSE_LAZY) {
+              sqzk::launch_index_parse_lazy(d_in, d_in_off, n, work_m, tokens, counts, slots, st);
+          } else {
+              sqzk::launch_index_parse(d_in, d_in_off, n, work_m, tokens, counts, slots, st);
+          } }
     }
 }
 
@@ -338,8 +347,8 @@ void run_encode(int finder, const uint8_t* d_in, const uint64_t* d_in_off, uint3
                 uint32_t window, uint32_t* tokens, uint32_t* counts, uint32_t* work_a,
                 uint32_t* work_m, uint64_t avg_block, uint8_t* d_out, const uint64_t* d_out_off,
                 uint64_t* d_out_bytes, int32_t* d_err, uint64_t prefix_acc, int prefix_fill,
-                uint64_t slots, sqz_block_stats* d_stats, hipStream_t st) {
-    run_stage1(finder, d_in, d_in_off, n, window, tokens, counts, work_a, work_m, avg_block, slots, st);
+                uint64_t slots, sqz_block_stats* d_stats, hipStream_t st, uint32_t parse = SQZ_PARSE_GREEDY) {
+    run_stage1(finder, d_in, d_in_off, n, window, tokens, counts, work_a, work_m, avg_block, slots, st, parse);
     SpanGuard g(st, SQZ_HIP_K_HUFFMAN_EMIT);
     sqzk::launch_huffman_emit(tokens, d_in_off, counts, d_out, d_out_off, d_out_bytes, d_err, n,
                               prefix_acc, prefix_fill, d_stats, st);
@@ -350,7 +359,8 @@ void run_encode(int finder, const uint8_t* d_in, const uint64_t* d_in_off, uint3
 int encode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_off, uint32_t n,
                        uint32_t window, uint8_t* out, const uint64_t* out_off,
                        uint64_t* out_bytes, int32_t* err,
-                       uint64_t prefix_acc, int prefix_fill, uint64_t* tokens_total) {
+                       uint64_t prefix_acc, int prefix_fill, uint64_t* tokens_total,
+                       uint32_t parse = SQZ_PARSE_GREEDY) {
     const uint64_t in_base = in_off[0], out_base = out_off[0];
     const uint64_t total_in = in_off[n] - in_base, total_out = out_off[n] - out_base;
     std::vector<uint64_t> io(n + 1), oo(n + 1);
@@ -369,10 +379,10 @@ int encode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_o
     HIP_TRY(hipMemcpyAsync(c.out_off.p, oo.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     uint64_t widest = 0;
     for (uint32_t b = 0; b < n; b++) { widest = io[b + 1] - io[b] > widest ? io[b + 1] - io[b] : widest; }
-    run_encode(finder_default(), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, n, window,
+    run_encode(finder_for(parse), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, n, window,
                (uint32_t*)c.work_a.p /* token words take the sorted positions' place */, (uint32_t*)c.tok_count.p,
                (uint32_t*)c.work_a.p, (uint32_t*)c.work_m.p, widest, (uint8_t*)c.out.p, (const uint64_t*)c.out_off.p,
-               (uint64_t*)c.out_bytes.p, (int32_t*)c.err.p, prefix_acc, prefix_fill, total_in + 64, nullptr, st);
+               (uint64_t*)c.out_bytes.p, (int32_t*)c.err.p, prefix_acc, prefix_fill, total_in + 64, nullptr, st, parse);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_bytes, c.out_bytes.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(err, c.err.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -545,7 +555,8 @@ FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_byt
 // the device side of a frame encode: everything enqueued on st, nothing waits
 int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
                      uint8_t* d_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
-                     int32_t* d_err, uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t flags = 0) {
+                     int32_t* d_err, uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t flags = 0,
+                     uint32_t parse = SQZ_PARSE_GREEDY) {
     const uint64_t bb = 1ull << block_bits, n64 = frame_blocks(content_bytes, block_bits);
     if (n64 > 0xFFFFFFFFull) { return EINVAL; }
     const uint32_t n = (uint32_t)n64;
@@ -570,8 +581,8 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
         const uint64_t slots = (L.codec_bytes - head) / 8;
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + head);
-        run_encode(finder_default(), d_in, in_off, n, 1u << win_bits, tokens, counts, tokens, tokens + slots, bb,
-                   scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st);
+        run_encode(finder_for(parse), d_in, in_off, n, 1u << win_bits, tokens, counts, tokens, tokens + slots, bb,
+                   scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st, parse);
     }
     { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
       if (store) {
@@ -942,6 +953,12 @@ squeeze_interface squeeze = {
 // ------------------------------------------------------------------ batch, host
 int sqz_encode_blocks(const uint8_t* in, const uint64_t* in_off, uint32_t n, uint32_t window,
                       uint8_t* out, const uint64_t* out_off, uint64_t* out_bytes, int32_t* err) {
+    return sqz_encode_blocks_parse(in, in_off, n, window, SQZ_PARSE_GREEDY, out, out_off, out_bytes, err);
+}
+
+int sqz_encode_blocks_parse(const uint8_t* in, const uint64_t* in_off, uint32_t n, uint32_t window, uint32_t parse,
+                            uint8_t* out, const uint64_t* out_off, uint64_t* out_bytes, int32_t* err) {
+    if (!parse_ok(parse)) { return EINVAL; }
     if (n == 0) { return 0; }
     if (in_off == NULL || out_off == NULL || out == NULL || out_bytes == NULL || err == NULL ||
         !window_ok(window)) { return EINVAL; }
@@ -951,7 +968,7 @@ int sqz_encode_blocks(const uint8_t* in, const uint64_t* in_off, uint32_t n, uin
     if (e != 0) { return e; }
     LaneLease lease;
     return encode_host(*lease.lane, lease.stream(nullptr), in, in_off, n, window, out, out_off, out_bytes, err,
-                       0, 0, nullptr);
+                       0, 0, nullptr, parse);
 }
 
 int sqz_decode_blocks(const uint8_t* in, const uint64_t* in_off, uint32_t n,
@@ -989,6 +1006,14 @@ int sqz_hip_lz77_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n, 
 int sqz_hip_lz77_blocks_ex(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window,
                            uint32_t* d_tokens, uint32_t* d_token_count, int finder,
                            void* d_work, uint64_t work_bytes, void* stream) {
+    return sqz_hip_lz77_blocks_parse(d_in, d_in_off, n, window, d_tokens, d_token_count, finder, SQZ_PARSE_GREEDY,
+                                     d_work, work_bytes, stream);
+}
+
+int sqz_hip_lz77_blocks_parse(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window,
+                              uint32_t* d_tokens, uint32_t* d_token_count, int finder, uint32_t parse,
+                              void* d_work, uint64_t work_bytes, void* stream) {
+    if (!parse_ok(parse) || (parse == SQZ_PARSE_LAZY && finder != 1)) { return EINVAL; }
     if (n == 0) { return 0; }
     if (d_in == NULL || d_in_off == NULL || d_tokens == NULL || d_token_count == NULL ||
         !window_ok(window) || (finder != 0 && finder != 1)) { return EINVAL; }
@@ -1001,7 +1026,7 @@ int sqz_hip_lz77_blocks_ex(const void* d_in, const uint64_t* d_in_off, uint32_t 
     uint32_t* wm = wa != nullptr ? wa + slots : nullptr;
     run_stage1(finder, (const uint8_t*)d_in, d_in_off, n, window, d_tokens, d_token_count,
                finder == 1 ? wa : nullptr, finder == 1 ? wm : nullptr,
-               slots / (n > 0 ? n : 1), finder == 1 ? slots : ~0ull, (hipStream_t)stream);
+               slots / (n > 0 ? n : 1), finder == 1 ? slots : ~0ull, (hipStream_t)stream, parse);
     return hip_errno(hipGetLastError());
 }
 
@@ -1027,6 +1052,18 @@ int sqz_hip_encode_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n
                                        d_scratch, scratch_bytes, NULL, stream);
 }
 
+static int encode_blocks_dev(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window, uint32_t parse,
+                             void* d_out, const uint64_t* d_out_off, uint64_t* d_out_bytes, int32_t* d_err,
+                             void* d_scratch, uint64_t scratch_bytes, sqz_block_stats* d_stats, void* stream);
+
+int sqz_hip_encode_blocks_parse(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window,
+                                uint32_t parse, void* d_out, const uint64_t* d_out_off, uint64_t* d_out_bytes,
+                                int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!parse_ok(parse)) { return EINVAL; }
+    return encode_blocks_dev(d_in, d_in_off, n, window, parse, d_out, d_out_off, d_out_bytes, d_err,
+                             d_scratch, scratch_bytes, NULL, stream);
+}
+
 double sqz_stats_entropy(const uint32_t* freq, uint32_t n) {          // huffman.h:237-249
     if (freq == NULL) { return 0.0; }
     double total = 0.0, e = 0.0;
@@ -1044,6 +1081,13 @@ int sqz_hip_encode_blocks_stats(const void* d_in, const uint64_t* d_in_off, uint
                                 void* d_out, const uint64_t* d_out_off, uint64_t* d_out_bytes,
                                 int32_t* d_err, void* d_scratch, uint64_t scratch_bytes,
                                 sqz_block_stats* d_stats, void* stream) {
+    return encode_blocks_dev(d_in, d_in_off, n, window, SQZ_PARSE_GREEDY, d_out, d_out_off, d_out_bytes, d_err,
+                             d_scratch, scratch_bytes, d_stats, stream);
+}
+
+static int encode_blocks_dev(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window, uint32_t parse,
+                             void* d_out, const uint64_t* d_out_off, uint64_t* d_out_bytes, int32_t* d_err,
+                             void* d_scratch, uint64_t scratch_bytes, sqz_block_stats* d_stats, void* stream) {
     if (n == 0) { return 0; }
     if (d_scratch == NULL || scratch_bytes < sqz_hip_encode_scratch_bytes(n, 0)) { return EINVAL; }
     if (d_in == NULL || d_in_off == NULL || d_out == NULL || d_out_off == NULL ||
@@ -1060,9 +1104,9 @@ int sqz_hip_encode_blocks_stats(const void* d_in, const uint64_t* d_in_off, uint
     uint32_t* tokens = (uint32_t*)((uint8_t*)d_scratch + head);
     uint32_t* work_a = tokens;                             // sorted positions first, the token words afterwards
     uint32_t* work_m = work_a + slots;
-    run_encode(finder_default(), (const uint8_t*)d_in, d_in_off, n, window, tokens, counts,
+    run_encode(finder_for(parse), (const uint8_t*)d_in, d_in_off, n, window, tokens, counts,
                work_a, work_m, slots / n, (uint8_t*)d_out, d_out_off, d_out_bytes, d_err, 0, 0,
-               slots, d_stats, (hipStream_t)stream);
+               slots, d_stats, (hipStream_t)stream, parse);
     return hip_errno(hipGetLastError());
 }
 
@@ -1322,6 +1366,14 @@ int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, u
 
 int sqz_frame_compress_ex(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits, uint32_t flags,
                           uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
+    return sqz_frame_compress_parse(data, bytes, win_bits, block_bits, flags, SQZ_PARSE_GREEDY, frame, capacity,
+                                    frame_bytes);
+}
+
+int sqz_frame_compress_parse(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                             uint32_t flags, uint32_t parse, uint8_t* frame, uint64_t capacity,
+                             uint64_t* frame_bytes) {
+    if (!parse_ok(parse)) { return EINVAL; }
     if (frame_bytes == NULL || (frame == NULL && capacity > 0) || (data == NULL && bytes > 0) ||
         !frame_params_ok(win_bits, block_bits) || !frame_flags_ok(flags)) { return EINVAL; }
     const bool store = (flags & SQZ_FRAME_STORED) != 0;
@@ -1353,10 +1405,10 @@ int sqz_frame_compress_ex(const uint8_t* data, uint64_t bytes, uint32_t win_bits
             sqzk::launch_frame_plan(pn, bb, total_in, slab, (uint64_t*)c.in_off.p, (uint64_t*)c.out_off.p, st);
             { SpanGuard g(st, SQZ_HIP_K_CRC32);
               sqzk::launch_crc32_blocks((const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, (uint32_t*)c.crc.p, bb, st); }
-            run_encode(finder_default(), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, 1u << win_bits,
+            run_encode(finder_for(parse), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, 1u << win_bits,
                        (uint32_t*)c.work_a.p, (uint32_t*)c.tok_count.p, (uint32_t*)c.work_a.p, (uint32_t*)c.work_m.p, bb,
                        (uint8_t*)c.out.p, (const uint64_t*)c.out_off.p, (uint64_t*)c.out_bytes.p, (int32_t*)c.err.p,
-                       0, 0, total_in + 64, nullptr, st);
+                       0, 0, total_in + 64, nullptr, st, parse);
             HIP_TRY(hipGetLastError());
             out_bytes.resize(pn); err.resize(pn); crc.resize(pn); dense_off.resize((size_t)pn + 1);
             HIP_TRY(hipMemcpyAsync(out_bytes.data(), c.out_bytes.p, (size_t)pn * 8, hipMemcpyDeviceToHost, st));
@@ -1489,6 +1541,15 @@ int sqz_hip_frame_encode(const void* d_in, uint64_t content_bytes, uint32_t win_
 int sqz_hip_frame_encode_ex(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
                             uint32_t flags, void* d_frame, uint64_t capacity, uint64_t* d_frame_bytes,
                             int32_t* d_status, int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return sqz_hip_frame_encode_parse(d_in, content_bytes, win_bits, block_bits, flags, SQZ_PARSE_GREEDY, d_frame,
+                                      capacity, d_frame_bytes, d_status, d_err, d_scratch, scratch_bytes, stream);
+}
+
+int sqz_hip_frame_encode_parse(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
+                               uint32_t flags, uint32_t parse, void* d_frame, uint64_t capacity,
+                               uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err, void* d_scratch,
+                               uint64_t scratch_bytes, void* stream) {
+    if (!parse_ok(parse)) { return EINVAL; }
     if (!frame_flags_ok(flags)) { return EINVAL; }
     if (!frame_params_ok(win_bits, block_bits) || (d_in == NULL && content_bytes > 0) || d_frame == NULL ||
         ((uintptr_t)d_frame & 15u) != 0 || d_frame_bytes == NULL || d_status == NULL ||
@@ -1497,7 +1558,7 @@ int sqz_hip_frame_encode_ex(const void* d_in, uint64_t content_bytes, uint32_t w
     if (e != 0) { return e; }
     return frame_encode_dev((const uint8_t*)d_in, content_bytes, win_bits, block_bits, (uint8_t*)d_frame, capacity,
                             d_frame_bytes, d_status, d_err, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
-                            flags);
+                            flags, parse);
 }
 
 int sqz_hip_frame_decode(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,

@@ -662,6 +662,14 @@ __device__ __forceinline__ uint32_t parse_step(uint32_t w) {
     return len != 0 ? len : 1u;
 }
 
+// The one-step lazy rule: a match gives way to a literal where the very next position holds a longer one
+// (w1 = the successor's word; a literal's length field is 0, so a successor without a match never wins).
+// The decision depends on the position alone, so the walks below stay walks of a step function.
+__device__ __forceinline__ bool lazy_defers(uint32_t w, uint32_t w1) {
+    const uint32_t len = w >> 16;
+    return len >= (uint32_t)kLenMin && (w1 >> 16) > len;
+}
+
 // A tile's match words as they travel: lane l holds positions l, l + 64, ... of the tile, one coalesced load each,
 // all issued back to back.  Positions past the stream's end read its last word again (clamped, never used).
 constexpr int kTileRows = kTile / kWave;
@@ -704,7 +712,26 @@ struct ParseSec {
 #define PARSE_SEC_LOADS(s, k)
 #endif
 
-// 117 VGPRs (a tile in flight, a chunk's words): the 4 waves per SIMD = 16 streams per CU that the LDS admits need <= 128
+// kLazy = false is the greedy parse, the reference's (and, instruction for instruction, the kernel this was before it
+// became a template); kLazy = true applies lazy_defers() on top of it.  The decision at a position depends on that
+// position alone, so the scheme stands: every lane first turns its chunk's words into a mask of the positions that
+// give way (`defer`), and the guess walks and the fix-up step by 1 where the mask says so.  The lazy instantiation
+// needs two things the greedy one does not:
+//   * the successor's word at every position.  Inside a chunk it is the next word of the row; at a chunk's last
+//     position it is the first word of the next lane's row, read straight from there; at the tile's last position
+//     it is the first word of the NEXT tile: one more load (33 per tile) that travels with the tile's own 32, a
+//     tile ahead like them.  Position bytes-2, and everything behind it, is a literal: nothing gives way to it.
+//   * the byte of a token start that gives way (a match word does not carry it).  These are a few per cent of the
+//     tokens, and the tile's bytes neither fit the LDS (8,448 B are what 16 streams per CU leave) nor the
+//     registers (8 words per lane held across the tile: 147 VGPRs).  After the fix-up every lane sends for the
+//     bytes of the first two such tokens of its chunk -- always two loads -- and writes them over the match
+//     tokens once those are packed in LDS; a chunk with more than two fetches the rest one by one.  The wait for
+//     them is a wait for loads that set out after the next tile's words and before this tile's token stores: it
+//     never waits for the stores, and the next tile's words have had the walks' time to arrive.
+//
+// gfx950, -Rpass-analysis=kernel-resource-usage: greedy 117 VGPRs, lazy 125; no scratch, no spills; 8,448 B of LDS
+// both.  The 4 waves per SIMD = 16 streams per CU that the LDS admits need <= 128.
+template <bool kLazy>
 __global__ __launch_bounds__(kWave)
 void index_parse_kernel(const uint8_t* __restrict__ in,
                         const uint64_t* __restrict__ in_off,
@@ -742,6 +769,13 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
     uint32_t entry = 0;                              // where the real path enters the tile (tile-relative)
     uint32_t fly[kTileRows];                         // the tile in flight
     parse_fetch(fly, M, 0, bytes, lane);
+    uint32_t fly_next = 0;                           // lazy: the first word of the tile behind the one in flight
+    // (the index goes through a vector register: the word comes by the same road as the others and is counted with them)
+    auto fetch_next = [&](const uint64_t tile) __attribute__((always_inline)) {
+        const uint64_t at = tile + (uint64_t)per_tile((uint32_t)kTile);
+        fly_next = M[at < bytes ? at : bytes - 1];
+    };
+    if constexpr (kLazy) { fetch_next(0); }
     // one tile; false: the path has left the stream (its last token reaches over the ragged last tile)
     auto do_tile = [&](const uint64_t tile) __attribute__((always_inline)) -> bool {
         const uint64_t left = bytes - tile;
@@ -756,22 +790,43 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
             const int tj = t2 - j * kWave;
             mine_at[j * (kWave + kWave / kChunk)] = lane < tj ? fly[j] : lane == tj ? lit2 : lit1;
         }
+        uint32_t over = 0;                           // lazy: the word behind the tile's last one, if that position can hold a match at all
+        if constexpr (kLazy) {
+            over = left > (uint64_t)(kTile + 2) ? fly_next : 0u;
+        }
         lds_barrier();
         // the next tile's words set out now and are taken up after this tile's tokens have left (behind the
         // last tile: the same tile once more, into registers nobody reads)
-        parse_fetch(fly, M, tile + (uint64_t)kTile < bytes ? tile + (uint64_t)kTile : tile, bytes, lane);
+        const uint64_t ahead = tile + (uint64_t)kTile < bytes ? tile + (uint64_t)kTile : tile;
+        parse_fetch(fly, M, ahead, bytes, lane);
+        if constexpr (kLazy) { fetch_next(ahead); }
         PARSE_SEC(sec, 1)
 
         // ---- every lane: its chunk from the chunk's first position ---------------------
         const uint32_t lo = (uint32_t)lane * (uint32_t)kChunk;
         const uint32_t room = have > lo ? (have - lo < (uint32_t)kChunk ? have - lo : (uint32_t)kChunk) : 0u;
         const uint32_t* row = &lds.m[lane * kChunkRow];
+        uint32_t defer = 0;                          // lazy: one bit per position of the chunk that gives way to its successor
+        if constexpr (kLazy) {                       // (a loop, eight words at a time: unrolled it holds the row in registers)
+            // the successor of the chunk's last word: the first word of the next lane's row, of the next tile for lane 63
+            const uint32_t behind = lane + 1 < kWave ? lds.m[(lane + 1 < kWave ? lane + 1 : lane) * kChunkRow] : over;
+            uint32_t w = row[0];
+#pragma unroll 1
+            for (int j0 = 0; j0 < kChunk; j0 += 8) {
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const uint32_t w1 = j0 + j + 1 < kChunk ? row[j0 + j + 1] : behind;
+                    defer |= (lazy_defers(w, w1) ? 1u : 0u) << (j0 + j);
+                    w = w1;
+                }
+            }
+        }
         uint32_t guess = 0;                          // one bit per position of the chunk (kChunk <= 32)
         uint32_t p = 0;
         while (p < room) {
             guess |= 1u << p;
             const uint32_t w = row[p];
-            p += parse_step(w);
+            if constexpr (kLazy) { p += ((defer >> p) & 1u) != 0 ? 1u : parse_step(w); } else { p += parse_step(w); }
         }
         const uint32_t guess_out = lo + p;           // where the guess leaves the chunk (>= lo + room)
         PARSE_SEC(sec, 2)
@@ -800,7 +855,12 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
             do {                                     // it was not: hop
                 real |= 1u << q;
                 const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds.m[l * kChunkRow + q]);
-                q += parse_step(w);
+                if constexpr (kLazy) {
+                    const uint32_t dl = (uint32_t)__builtin_amdgcn_readlane((int)defer, (int)l);
+                    q += ((dl >> q) & 1u) != 0 ? 1u : parse_step(w);
+                } else {
+                    q += parse_step(w);
+                }
             } while (q < croom && ((g >> q) & 1u) == 0);
             const bool met = q < croom;              // on a position of the guess (which has none at or beyond croom)
             e = met ? (uint32_t)__builtin_amdgcn_readlane((int)guess_out, (int)l) : clo + q;
@@ -808,6 +868,20 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
         }
         const uint32_t mine = extra | (from < (uint32_t)kChunk ? guess & (~0u << from) : 0u);   // this lane's chunk: real token starts
         entry = e - (uint32_t)kTile;                 // e >= have here; carried into the next tile
+        // lazy: the token starts that give way are literals of their bytes, which no match word carries.  They are a
+        // few per cent of the tokens: every lane sends for the first two of its chunk here -- always two loads, so
+        // that the waits stay counted ones -- and writes them over the match tokens further down; a chunk with more
+        // (rare) fetches the rest there, one by one.
+        uint32_t give = 0, give_j0 = 0, give_j1 = 0, give_b0 = 0, give_b1 = 0;
+        if constexpr (kLazy) {
+            give = mine & defer;
+            const uint32_t second = give & (give - 1u);
+            give_j0 = give != 0 ? (uint32_t)__builtin_ctz(give) : 0u;
+            give_j1 = second != 0 ? (uint32_t)__builtin_ctz(second) : give_j0;
+            const uint64_t at0 = tile + (uint64_t)(lo + give_j0), at1 = tile + (uint64_t)(lo + give_j1);
+            give_b0 = src[at0 < bytes ? at0 : bytes - 1];        // (a lane without any reads a byte it does not use)
+            give_b1 = src[at1 < bytes ? at1 : bytes - 1];
+        }
         PARSE_SEC(sec, 3)
 
         // ---- token words, in order ----------------------------------------------------
@@ -828,6 +902,18 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
         for (int j = 0; j < kChunk; j++) {
             if ((mine >> j) & 1u) {
                 lds.m[at++] = (mw[j] >> 16) != 0 ? (kTokMatch | mw[j]) : (mw[j] & 0xFFu);
+            }
+        }
+        if constexpr (kLazy) {                       // token n of the chunk is the n-th set bit of `mine`
+            const uint32_t first = incl - cnt;
+            auto slot_of = [&](uint32_t j) { return first + (uint32_t)__builtin_popcount(mine & ((1u << j) - 1u)); };
+            uint32_t rest = give;
+            if (rest != 0) { lds.m[slot_of(give_j0)] = give_b0; rest &= rest - 1u; }
+            if (rest != 0) { lds.m[slot_of(give_j1)] = give_b1; rest &= rest - 1u; }
+            while (rest != 0) {
+                const uint32_t j = (uint32_t)__builtin_ctz(rest);
+                rest &= rest - 1u;
+                lds.m[slot_of(j)] = (uint32_t)src[tile + (uint64_t)(lo + j)];
             }
         }
         lds_barrier();
@@ -886,7 +972,15 @@ void launch_index_parse(const uint8_t* in, const uint64_t* in_off, uint32_t n_bl
                         const uint32_t* match, uint32_t* tokens, uint32_t* tok_count,
                         uint64_t slots, hipStream_t stream) {
     if (n_blocks == 0) { return; }
-    hipLaunchKernelGGL(index_parse_kernel, dim3(n_blocks), dim3(kWave), 0, stream,
+    hipLaunchKernelGGL(index_parse_kernel<false>, dim3(n_blocks), dim3(kWave), 0, stream,
+                       in, in_off, n_blocks, match, tokens, tok_count, slots);
+}
+
+void launch_index_parse_lazy(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
+                             const uint32_t* match, uint32_t* tokens, uint32_t* tok_count,
+                             uint64_t slots, hipStream_t stream) {
+    if (n_blocks == 0) { return; }
+    hipLaunchKernelGGL(index_parse_kernel<true>, dim3(n_blocks), dim3(kWave), 0, stream,
                        in, in_off, n_blocks, match, tokens, tok_count, slots);
 }
 

@@ -32,6 +32,10 @@ void launch_index_match(const uint8_t* in, const uint64_t* in_off, uint32_t n_bl
 void launch_index_parse(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
                         const uint32_t* match, uint32_t* tokens, uint32_t* tok_count,
                         uint64_t slots, hipStream_t stream);
+// the one-step lazy parse over the same match table (not the reference's token sequence; any decoder reads it)
+void launch_index_parse_lazy(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
+                             const uint32_t* match, uint32_t* tokens, uint32_t* tok_count,
+                             uint64_t slots, hipStream_t stream);
 
 // stage 2: adaptive-Huffman emit (squeeze.h:278-315, huffman.h, bitstream.h)
 void launch_huffman_emit(const uint32_t* tokens, const uint64_t* tok_off,

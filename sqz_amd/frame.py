@@ -3,18 +3,20 @@
 Host flavour (bytes in, bytes out) and a device flavour over torch tensors in the style of batch.py.
 Every byte of codec and checksum work happens in libsqz_amd.so; nothing is computed here.
 
-    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18] [--store]    compress a file
+    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18] [--store] [--lazy]    compress a file
     python -m sqz_amd.frame d IN OUT                                       decompress one
     python -m sqz_amd.frame info IN                                        describe one
     python -m sqz_amd.frame blocks IN                                      one line per block
 
 store=True / --store writes version 2: a block whose stream is not smaller than its content is stored as it is.
+parse="lazy" / --lazy encodes with one position of look-ahead (codec.parse_code): smaller streams in the same frame
+format, read by every reader; the default, "greedy", is the reference's parse.
 """
 import ctypes as C
 import errno
 
 from . import _native as N
-from .codec import SqzError, _raise
+from .codec import PARSE_LAZY, SqzError, _raise, parse_code
 
 HEADER_BYTES = 32
 FRAME_STORED = 1            # SQZ_FRAME_STORED
@@ -48,7 +50,9 @@ def frame_blocks(frame) -> list:
     return [{k: int(getattr(out[b], k)) for k, _ in N.FrameBlock._fields_} for b in range(n)]
 
 
-def compress_frame(data, win_bits: int = 15, block_bits: int = 18, store: bool = False) -> bytes:
+def compress_frame(data, win_bits: int = 15, block_bits: int = 18, store: bool = False,
+                   parse: str = "greedy") -> bytes:
+    lazy = parse_code(parse) == PARSE_LAZY
     data = bytes(data)
     cap = frame_bound(len(data), block_bits, store)
     if cap == 0:
@@ -56,8 +60,12 @@ def compress_frame(data, win_bits: int = 15, block_bits: int = 18, store: bool =
     out = bytearray(cap)
     n = C.c_uint64(0)
     dst = (C.c_uint8 * cap).from_buffer(out)
-    _raise(N.lib().sqz_frame_compress_ex(data, len(data), win_bits, block_bits, _flags(store), dst, cap, C.byref(n)),
-           "sqz_frame_compress_ex")
+    if lazy:
+        _raise(N.lib().sqz_frame_compress_parse(data, len(data), win_bits, block_bits, _flags(store), PARSE_LAZY, dst,
+                                                cap, C.byref(n)), "sqz_frame_compress_parse")
+    else:
+        _raise(N.lib().sqz_frame_compress_ex(data, len(data), win_bits, block_bits, _flags(store), dst, cap,
+                                             C.byref(n)), "sqz_frame_compress_ex")
     del dst
     return bytes(out[:n.value])
 
@@ -121,8 +129,9 @@ class FrameEncoder:
     encode() enqueues and returns; frame_bytes / status / err are device tensors to read after a synchronise."""
 
     def __init__(self, content_bytes: int, win_bits: int = 15, block_bits: int = 18, capacity: int = None,
-                 device="cuda", store: bool = False):
+                 device="cuda", store: bool = False, parse: str = "greedy"):
         import torch
+        self.parse = parse_code(parse)
         L = N.lib()
         self.win_bits, self.block_bits, self.content_bytes = win_bits, block_bits, content_bytes
         self.flags = _flags(store)
@@ -139,6 +148,12 @@ class FrameEncoder:
         nbytes = d_in.numel() if content_bytes is None else content_bytes
         if nbytes > self.content_bytes:
             raise SqzError(errno.E2BIG, "FrameEncoder: more content than the buffers were made for")
+        if self.parse == PARSE_LAZY:
+            _raise(N.lib().sqz_hip_frame_encode_parse(
+                _ptr(d_in), nbytes, self.win_bits, self.block_bits, self.flags, self.parse, _ptr(self.frame),
+                self.capacity, _ptr(self.frame_bytes), _ptr(self.status), _ptr(self.err), _ptr(self.scratch),
+                self.scratch_bytes, _stream()), "sqz_hip_frame_encode_parse")
+            return self.frame, self.frame_bytes, self.status, self.err
         _raise(N.lib().sqz_hip_frame_encode_ex(
             _ptr(d_in), nbytes, self.win_bits, self.block_bits, self.flags, _ptr(self.frame), self.capacity,
             _ptr(self.frame_bytes), _ptr(self.status), _ptr(self.err), _ptr(self.scratch), self.scratch_bytes,
@@ -193,6 +208,7 @@ def main(argv=None) -> int:
     c.add_argument("--win-bits", type=int, default=15)
     c.add_argument("--block-bits", type=int, default=18)
     c.add_argument("--store", action="store_true", help="version 2: store a block whose stream is not smaller")
+    c.add_argument("--lazy", action="store_true", help="lazy parse: smaller streams, same format (not the reference's bytes)")
     d = sub.add_parser("d", help="decompress IN to OUT")
     d.add_argument("src")
     d.add_argument("dst")
@@ -205,7 +221,7 @@ def main(argv=None) -> int:
         blob = fh.read()
     try:
         if a.cmd == "c":
-            out = compress_frame(blob, a.win_bits, a.block_bits, a.store)
+            out = compress_frame(blob, a.win_bits, a.block_bits, a.store, "lazy" if a.lazy else "greedy")
         elif a.cmd == "d":
             out = decompress_frame(blob)
         elif a.cmd == "blocks":
