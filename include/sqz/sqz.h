@@ -369,7 +369,8 @@ enum {
     sqz_frame_min_block_bits = 12,
     sqz_frame_max_block_bits = 24
 };
-enum { SQZ_FRAME_STORED = 1 };   /* flags: store a block raw when its stream is not smaller (version 2) */
+enum { SQZ_FRAME_STORED = 1,     /* flags: store a block raw when its stream is not smaller (version 2) */
+       SQZ_FRAME_DICT = 2 };     /* flags: every block may reach back into one shared dictionary (version 3, below) */
 struct sqz_frame_info {
     uint64_t content_bytes, payload_bytes, payload_off, frame_bytes, block_bytes;
     uint32_t n_blocks, win_bits, version, reserved;     /* reserved: the header's flags */
@@ -386,7 +387,7 @@ struct sqz_frame_block {
  * outside 12..24 */
 SQZ_API uint64_t sqz_frame_bound(uint64_t content_bytes, uint32_t block_bits);
 /* the same for a frame written with `flags`: sqz_frame_bound for 0; for SQZ_FRAME_STORED
- * pad16(32 + 8n) + round_up_8(content_bytes); 0 for any other flags */
+ * pad16(32 + 8n) + round_up_8(content_bytes); 0 for any other flags (a version-3 frame: sqz_frame_bound_dict) */
 SQZ_API uint64_t sqz_frame_bound_ex(uint64_t content_bytes, uint32_t block_bits, uint32_t flags);
 /* Parses and checks the header from the first `avail` bytes (E2BIG when avail < 32): magic,
  * version, flags, the ranges of win_bits / block_bits, n_blocks == ceil(content_bytes /
@@ -504,6 +505,82 @@ SQZ_API int sqz_hip_frame_encode_parse(const void* d_in, uint64_t content_bytes,
                                        uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
                                        int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* A shared dictionary: frames of SMALL blocks that still compress.  A ranged read pays off with small blocks (a
+ * block is one wave's dependent chain), and small blocks compress badly: each starts with empty trees and an empty
+ * window.  The caller supplies one dictionary of 1 .. window - 1 bytes, and every block may reach back into it as
+ * if it stood directly in front of the block: the stream of block B under dictionary Dct is exactly what the
+ * reference's encoder writes for the bytes Dct || B when it starts, with fresh trees, at position D = len(Dct).
+ * At block position i the candidates are the distances 1 .. min(D + i, window - 1), nearest first, a candidate
+ * replaces the best only when strictly longer, lengths count up to min(len(B) - i, 257), and a source may begin in
+ * the dictionary and run on into the block.  Tokens, entropy stage and stream format are unchanged (a distance is
+ * still at most 0x7FFF); blocks stay independent of each other.  The caller keeps the dictionary: it is not
+ * carried in the stream or the frame.  Opt-in like the lazy parse, and for the same reason: text gains 10-25 % at
+ * 1-16 KB blocks, an executable with its own header as dictionary LOSES 6 % (the greedy rule takes every 3-byte
+ * match, however far away).  The caller chooses the dictionary.
+ *
+ * Every call is its counterpart plus `dict, dict_bytes` (the encode calls also take `parse`), with the same
+ * errors otherwise.  dict == NULL, dict_bytes == 0 and dict_bytes > window - 1 (decode calls, which have no
+ * window: > 32767) are EINVAL at the call: nothing is launched.  The scan finder has no match table to merge the
+ * dictionary's matches into: sqz_hip_lz77_blocks_dict with finder 0 is EINVAL, and the encode calls run the
+ * indexed finder whatever sqz_hip_set_finder says.  Device flavour: d_dict is a device pointer.  The encode
+ * scratch grows by the dictionary's index, built once per call by index_sort_kernel:
+ *     sqz_hip_encode_scratch_bytes_dict(n, total, D) = sqz_hip_encode_scratch_bytes(n, total)
+ *                                                      + 256 + 2 * round_up_256(4 * (D + 64))      (<= 262,912)
+ * and sqz_hip_lz77_blocks_dict's d_work by the same amount (d_work and d_scratch 16-byte aligned).  A decode
+ * needs the scratch of sqz_hip_decode_blocks.  The decoder refuses a distance that reaches in front of the
+ * dictionary (dist > position + dict_bytes) with EINVAL for that block, as it refuses dist > position without.  */
+SQZ_API int sqz_encode_blocks_dict(const uint8_t* in, const uint64_t* in_off, uint32_t n, uint32_t window,
+                                   uint32_t parse, const uint8_t* dict, uint64_t dict_bytes, uint8_t* out,
+                                   const uint64_t* out_off, uint64_t* out_bytes, int32_t* err);
+SQZ_API int sqz_decode_blocks_dict(const uint8_t* in, const uint64_t* in_off, uint32_t n, const uint8_t* dict,
+                                   uint64_t dict_bytes, uint8_t* out, const uint64_t* out_off, int32_t* err);
+SQZ_API uint64_t sqz_hip_encode_scratch_bytes_dict(uint32_t n, uint64_t total_in_bytes, uint64_t dict_bytes);
+SQZ_API int sqz_hip_encode_blocks_dict(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window,
+                                       uint32_t parse, const void* d_dict, uint64_t dict_bytes, void* d_out,
+                                       const uint64_t* d_out_off, uint64_t* d_out_bytes, int32_t* d_err,
+                                       void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API int sqz_hip_decode_blocks_dict(const void* d_in, const uint64_t* d_in_off, uint32_t n, const void* d_dict,
+                                       uint64_t dict_bytes, void* d_out, const uint64_t* d_out_off, int32_t* d_err,
+                                       void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API int sqz_hip_lz77_blocks_dict(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window,
+                                     uint32_t* d_tokens, uint32_t* d_token_count, int finder, uint32_t parse,
+                                     const void* d_dict, uint64_t dict_bytes, void* d_work, uint64_t work_bytes,
+                                     void* stream);
+
+/* SQZF version 3 = version 2's layout with flags bit 1 (SQZ_FRAME_DICT) and one 8-byte record directly behind the
+ * n index entries:
+ *
+ *   4         1   version = 3.  A header is version 3 iff bit 1 of flags is set: version 3 without it or with any
+ *                 of bits 2..7, and version 1 or 2 with bit 1, are EINVAL.  Bit 0 (SQZ_FRAME_STORED) may accompany
+ *                 it with its unchanged rule, stored iff stream_bytes(b) >= length(b); a stored block ignores the
+ *                 dictionary, and a stored entry in a frame without bit 0 is EINVAL.
+ *   32 + 8n   4   dict_bytes    1 .. window - 1 (anything else EINVAL)
+ *   36 + 8n   4   dict_crc      CRC-32 (zlib) of the dictionary
+ *   ..            zero padding to the next multiple of 16 -> payload_off = pad16(32 + 8n + 8)
+ *
+ * index_crc covers bytes [0,28), the index and the record.  A frame written without a dictionary is byte for
+ * byte what it always was.  sqz_frame_info and sqz_frame_blocks accept version 3 (struct sqz_frame_info is
+ * unchanged: version = 3, reserved = flags); sqz_frame_dict reads the record (EINVAL for versions 1 and 2, E2BIG
+ * when avail does not cover it); sqz_frame_bound_dict is the worst case of a frame written by
+ * sqz_frame_compress_dict with the same flags (sqz_frame_bound_ex's with the record's 8 bytes in front of the
+ * padding; sqz_frame_bound_ex itself keeps answering 0 for any flag but SQZ_FRAME_STORED).
+ * Host flavour only.  compress_dict: flags 0 or SQZ_FRAME_STORED, with or without SQZ_FRAME_DICT, which is set in
+ * the header either way.  The dictionary is uploaded and indexed once per call, not once per pass.  A _dict
+ * reader first compares dict_bytes and the CRC-32 of the dictionary it was given with the record: a mismatch is
+ * EILSEQ for the call and for every block (block_err), nothing is decoded and nothing is written; a frame of
+ * version 1 or 2 is EINVAL.  sqz_frame_decompress and sqz_frame_read answer EINVAL for a version-3 frame.
+ * The device-resident flavour does not know version 3 yet: sqz_hip_frame_encode* with SQZ_FRAME_DICT are EINVAL,
+ * and sqz_hip_frame_decode refuses a version-3 frame by arithmetic (*d_status = EINVAL, nothing decoded).   */
+SQZ_API int sqz_frame_dict(const uint8_t* frame, uint64_t avail, uint32_t* dict_bytes, uint32_t* dict_crc);
+SQZ_API uint64_t sqz_frame_bound_dict(uint64_t content_bytes, uint32_t block_bits, uint32_t flags);
+SQZ_API int sqz_frame_compress_dict(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                                    uint32_t flags, uint32_t parse, const uint8_t* dict, uint64_t dict_bytes,
+                                    uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes);
+SQZ_API int sqz_frame_decompress_dict(const uint8_t* frame, uint64_t avail, const uint8_t* dict, uint64_t dict_bytes,
+                                      uint8_t* data, uint64_t capacity, uint64_t* bytes, int32_t* block_err);
+SQZ_API int sqz_frame_read_dict(const uint8_t* frame, uint64_t avail, const uint8_t* dict, uint64_t dict_bytes,
+                                uint64_t offset, uint64_t length, uint8_t* out);
+
 /* Live timing of the last kernels enqueued through this library on the
  * calling thread's context, measured with HIP events ON THE LAUNCH STREAM.
  * Enabled with sqz_hip_set_timing(1); values in milliseconds.               */
@@ -511,7 +588,9 @@ enum {
     SQZ_HIP_K_LZ77_SCAN = 0,      /* lz77_scan_kernel (brute-force finder)            */
     SQZ_HIP_K_HUFFMAN_EMIT = 1,   /* huffman_emit_kernel                              */
     SQZ_HIP_K_ENTROPY_DECODE = 2, /* entropy_decode_kernel                            */
-    SQZ_HIP_K_INDEX_SORT = 3,     /* index_sort_kernel   } indexed finder             */
+    SQZ_HIP_K_INDEX_SORT = 3,     /* index_sort_kernel   } indexed finder; a _dict encode call also sorts its dictionary
+                                   * under this slot: two launches per call, their times summed (no slot is free for
+                                   * dict_match_kernel, which is not timed here)                                      */
     SQZ_HIP_K_INDEX_MATCH = 4,    /* index_match_kernel  }                            */
     SQZ_HIP_K_INDEX_PARSE = 5,    /* index_parse_kernel  }                            */
     SQZ_HIP_K_LZ_EXPAND = 6,      /* lz_expand_kernel                                 */

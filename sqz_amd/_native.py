@@ -152,6 +152,22 @@ PROTOTYPES = {
                                            C.c_uint64, _u64p]),
     "sqz_hip_frame_encode_parse": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
                                              C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_encode_blocks_dict": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp,
+                                         _vp]),
+    "sqz_decode_blocks_dict": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "sqz_hip_encode_scratch_bytes_dict": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint64]),
+    "sqz_hip_encode_blocks_dict": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp,
+                                             _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_decode_blocks_dict": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64,
+                                             _vp]),
+    "sqz_hip_lz77_blocks_dict": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_int, C.c_uint32, _vp,
+                                           C.c_uint64, _vp, C.c_uint64, _vp]),
+    "sqz_frame_dict": (C.c_int, [_vp, C.c_uint64, _u32p, _u32p]),
+    "sqz_frame_bound_dict": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "sqz_frame_compress_dict": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                          C.c_uint64, _vp, C.c_uint64, _u64p]),
+    "sqz_frame_decompress_dict": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
+    "sqz_frame_read_dict": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp]),
     "sqz_hip_set_finder": (None, [C.c_int]),
     "sqz_hip_get_finder": (C.c_int, []),
     "sqz_hip_set_timing": (None, [C.c_int]),

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .codec import PARSE_LAZY, SqzError, _raise, parse_code
+from .codec import PARSE_LAZY, SqzError, _raise, dict_bytes, parse_code
 
 
 def _ptr(t):
@@ -18,6 +18,18 @@ def _ptr(t):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _dict_tensor(dictionary, window, device):
+    """a shared dictionary (bytes-like) checked and on the device"""
+    d = dict_bytes(dictionary, window)
+    return torch.frombuffer(bytearray(d), dtype=torch.uint8).to(device)
+
+
+def _dict_index_bytes(n: int) -> int:
+    """what a dictionary of n bytes adds to an encode's scratch (its index, include/sqz/sqz.h)"""
+    L = N.lib()
+    return int(L.sqz_hip_encode_scratch_bytes_dict(0, 0, n)) - int(L.sqz_hip_encode_scratch_bytes(0, 0))
 
 
 def uniform_offsets(n_blocks: int, block_bytes: int, device="cuda"):
@@ -49,8 +61,22 @@ class Encoder:
         self.scratch_bytes = int(L.sqz_hip_encode_scratch_bytes(n_blocks, total_bytes))
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=device)
 
-    def encode(self, d_in, in_off, window: int, parse: str = "greedy"):
-        """parse: "greedy" = the reference's streams, "lazy" = smaller ones of the same format (codec.parse_code)"""
+    def encode(self, d_in, in_off, window: int, parse: str = "greedy", dictionary=None):
+        """parse: "greedy" = the reference's streams, "lazy" = smaller ones of the same format (codec.parse_code).
+        dictionary: bytes-like of 1 .. window - 1 bytes that every block may reach back into (DESIGN.md section 10,
+        "Version 3"); None is the call without one."""
+        if dictionary is not None:
+            d = _dict_tensor(dictionary, window, self.device)
+            L = N.lib()
+            need = self.scratch_bytes + _dict_index_bytes(d.numel())
+            if getattr(self, "_dict_scratch", None) is None or self._dict_scratch.numel() < need:
+                self._dict_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _raise(L.sqz_hip_encode_blocks_dict(
+                _ptr(d_in), _ptr(in_off), self.n, window, parse_code(parse), _ptr(d), d.numel(), _ptr(self.out),
+                _ptr(self.out_off), _ptr(self.out_bytes), _ptr(self.err), _ptr(self._dict_scratch), need,
+                _stream()), "sqz_hip_encode_blocks_dict")
+            torch.cuda.current_stream().synchronize()       # (the dictionary's tensor lives until here)
+            return self.out, self.out_off, self.out_bytes, self.err
         if parse_code(parse) == PARSE_LAZY:
             _raise(N.lib().sqz_hip_encode_blocks_parse(
                 _ptr(d_in), _ptr(in_off), self.n, window, PARSE_LAZY, _ptr(self.out), _ptr(self.out_off),
@@ -82,7 +108,7 @@ class Encoder:
             res.append(d)
         return self.out, self.out_off, self.out_bytes, self.err, res
 
-    def tokens(self, d_in, in_off, window: int, finder: str = "index", parse: str = "greedy"):
+    def tokens(self, d_in, in_off, window: int, finder: str = "index", parse: str = "greedy", dictionary=None):
         """stage 1 alone: (tokens int32[total], counts int32[n]).
 
         finder: "scan" = brute force as the reference writes it, "index" = same
@@ -94,6 +120,18 @@ class Encoder:
         total = int(in_off[-1].item())
         toks = torch.zeros(total + 64, dtype=torch.int32, device=self.device)
         counts = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        if dictionary is not None:
+            if finder == "scan":
+                raise ValueError('dictionary= needs finder="index": the scan has no match table')
+            d = _dict_tensor(dictionary, window, self.device)
+            L = N.lib()
+            head = _dict_index_bytes(d.numel())
+            work = torch.empty(head + 8 * (total + 64), dtype=torch.uint8, device=self.device)
+            _raise(L.sqz_hip_lz77_blocks_dict(_ptr(d_in), _ptr(in_off), self.n, window, _ptr(toks), _ptr(counts), 1,
+                                              parse_code(parse), _ptr(d), d.numel(), _ptr(work), work.numel(),
+                                              _stream()), "sqz_hip_lz77_blocks_dict")
+            torch.cuda.synchronize()
+            return toks, counts
         if finder == "scan":
             _raise(N.lib().sqz_hip_lz77_blocks(_ptr(d_in), _ptr(in_off), self.n, window,
                                                 _ptr(toks), _ptr(counts), _stream()),
@@ -132,9 +170,9 @@ def pack_blocks(slabs, slab_off, sizes, dense=None):
 _decode_scratch = {}
 
 
-def decode_blocks(d_comp, comp_off, n_blocks, d_out, out_off, err=None, scratch=None):
+def decode_blocks(d_comp, comp_off, n_blocks, d_out, out_off, err=None, scratch=None, dictionary=None):
     """n streams -> d_out.  scratch: uint8 tensor of sqz_hip_decode_scratch_bytes()
-    (kept per device between calls when not given)."""
+    (kept per device between calls when not given).  dictionary: the bytes-like the streams were encoded under."""
     L = N.lib()
     if err is None:
         err = torch.zeros(n_blocks, dtype=torch.int32, device=d_out.device)
@@ -145,6 +183,13 @@ def decode_blocks(d_comp, comp_off, n_blocks, d_out, out_off, err=None, scratch=
         if scratch is None or scratch.numel() < need:
             scratch = torch.empty(need, dtype=torch.uint8, device=d_out.device)
             _decode_scratch[key] = scratch
+    if dictionary is not None:
+        d = _dict_tensor(dictionary, None, d_out.device)
+        _raise(L.sqz_hip_decode_blocks_dict(_ptr(d_comp), _ptr(comp_off), n_blocks, _ptr(d), d.numel(), _ptr(d_out),
+                                            _ptr(out_off), _ptr(err), _ptr(scratch), scratch.numel(),
+                                            _stream()), "sqz_hip_decode_blocks_dict")
+        torch.cuda.current_stream().synchronize()           # (the dictionary's tensor lives until here)
+        return err
     _raise(L.sqz_hip_decode_blocks(_ptr(d_comp), _ptr(comp_off), n_blocks, _ptr(d_out),
                                    _ptr(out_off), _ptr(err), _ptr(scratch), scratch.numel(),
                                    _stream()), "sqz_hip_decode_blocks")
@@ -169,9 +214,11 @@ def get_timing(reset=True):
 
 
 # ---- host-buffer flavour (numpy in / numpy out) ------------------------------
-def encode_blocks_host(blocks, window: int, capacity=None, parse: str = "greedy"):
-    """blocks: list of bytes-like.  Returns (list of compressed bytes, err array).  parse: codec.parse_code."""
+def encode_blocks_host(blocks, window: int, capacity=None, parse: str = "greedy", dictionary=None):
+    """blocks: list of bytes-like.  Returns (list of compressed bytes, err array).  parse: codec.parse_code.
+    dictionary: bytes-like of 1 .. window - 1 bytes shared by all blocks, or None."""
     lazy = parse_code(parse) == PARSE_LAZY
+    dct = dict_bytes(dictionary, window) if dictionary is not None else None
     L = N.lib()
     n = len(blocks)
     sizes = [len(b) for b in blocks]
@@ -185,7 +232,10 @@ def encode_blocks_host(blocks, window: int, capacity=None, parse: str = "greedy"
     out_bytes = np.zeros(n, np.uint64)
     err = np.zeros(n, np.int32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    if lazy:
+    if dct is not None:
+        _raise(L.sqz_encode_blocks_dict(p(data), p(in_off), n, window, parse_code(parse), dct, len(dct), p(out),
+                                        p(out_off), p(out_bytes), p(err)), "sqz_encode_blocks_dict")
+    elif lazy:
         _raise(L.sqz_encode_blocks_parse(p(data), p(in_off), n, window, PARSE_LAZY, p(out), p(out_off), p(out_bytes),
                                          p(err)), "sqz_encode_blocks_parse")
     else:
@@ -195,7 +245,8 @@ def encode_blocks_host(blocks, window: int, capacity=None, parse: str = "greedy"
     return res, err
 
 
-def decode_blocks_host(comps, sizes):
+def decode_blocks_host(comps, sizes, dictionary=None):
+    dct = dict_bytes(dictionary) if dictionary is not None else None
     L = N.lib()
     n = len(comps)
     in_off = np.zeros(n + 1, np.uint64)
@@ -206,6 +257,10 @@ def decode_blocks_host(comps, sizes):
     out = np.zeros(max(int(out_off[-1]), 1), np.uint8)
     err = np.zeros(n, np.int32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    _raise(L.sqz_decode_blocks(p(data), p(in_off), n, p(out), p(out_off), p(err)),
-           "sqz_decode_blocks")
+    if dct is not None:
+        _raise(L.sqz_decode_blocks_dict(p(data), p(in_off), n, dct, len(dct), p(out), p(out_off), p(err)),
+               "sqz_decode_blocks_dict")
+    else:
+        _raise(L.sqz_decode_blocks(p(data), p(in_off), n, p(out), p(out_off), p(err)),
+               "sqz_decode_blocks")
     return [out[int(out_off[b]):int(out_off[b + 1])].tobytes() for b in range(n)], err

@@ -32,6 +32,19 @@ def parse_code(parse: str) -> int:
     raise ValueError(f'parse must be "greedy" or "lazy", not {parse!r}')
 
 
+MAX_DICT_BYTES = (1 << MAX_WIN_BITS) - 1
+
+
+def dict_bytes(dictionary, window: int = None) -> bytes:
+    """A shared dictionary as bytes, checked before anything native is called: 1 .. window - 1 bytes
+    (1 .. 32767 where the call has no window)."""
+    d = bytes(dictionary)
+    most = MAX_DICT_BYTES if window is None else min(window - 1, MAX_DICT_BYTES)
+    if not 1 <= len(d) <= most:
+        raise ValueError(f"dictionary must be 1 .. {most} bytes, not {len(d)}")
+    return d
+
+
 def _raise(code, what):
     if code != 0:
         raise SqzError(code, f"{what}: {errno.errorcode.get(code, code)}")

@@ -21,6 +21,7 @@
 namespace {
 
 constexpr uint64_t kMaxStream = 1ull << 31;     // per-stream limit (32-bit freq/tokens)
+constexpr uint32_t sqzk_max_window = 1u << sqz_max_win_bits;   // a decode call has no window: the largest one bounds its dictionary
 
 // ---------------------------------------------------------------- device ctx
 struct DevBuf {
@@ -58,7 +59,7 @@ struct Lane {
     hipStream_t own = nullptr;      // created with the lane (non-blocking: independent of the NULL stream)
     int device = -1;                // hipGetDevice() when the lane was made: its buffers and stream live there
     DevBuf in, out, in_off, out_off, tokens, tok_count, out_bytes, err, end_bit, work_a, work_m,
-           dense, dense_off, crc, misc;
+           dense, dense_off, crc, misc, dict, dict_idx, mask;
     std::vector<uint8_t> host_dense;   // landing area of the host flavour's one device-to-host copy
 };
 
@@ -315,12 +316,47 @@ bool parse_ok(uint32_t parse) { return parse == SQZ_PARSE_GREEDY || parse == SQZ
 // the lazy parse reads the match table, which only the indexed finder writes: it runs that finder whatever is set
 int finder_for(uint32_t parse) { return parse == SQZ_PARSE_LAZY ? 1 : finder_default(); }
 
+// A call's shared dictionary on the device: its bytes and, for an encode, its positions sorted by 3-byte prefix.
+struct DictDev { const uint8_t* bytes = nullptr; uint32_t len = 0; const uint32_t* sorted = nullptr; };
+bool dict_ok(const void* dict, uint64_t dict_bytes, uint32_t window) {
+    return dict != NULL && dict_bytes >= 1 && window >= 2 && dict_bytes <= (uint64_t)window - 1;
+}
+// what the dictionary's index takes of an encode's scratch: the sort's one-block offsets and its two buffers
+uint64_t dict_slot_bytes(uint64_t dict_bytes) { return align_up((dict_bytes + 64) * 4, 256); }
+uint64_t dict_index_bytes(uint64_t dict_bytes) { return 256 + 2 * dict_slot_bytes(dict_bytes); }
+// index_sort_kernel on the dictionary as a one-block batch, once per call; area: dict_index_bytes, 16-byte aligned
+DictDev run_dict_index(const uint8_t* d_dict, uint32_t dict_bytes, uint8_t* area, hipStream_t st) {
+    uint64_t* const off = (uint64_t*)area;                   // {0, D}, written on the device: no host copy to wait for
+    uint32_t* const a = (uint32_t*)(area + 256);
+    uint32_t* const b = (uint32_t*)(area + 256 + dict_slot_bytes(dict_bytes));
+    sqzk::launch_frame_plan(1, dict_bytes, dict_bytes, 0, off, off + 4, st);
+    SpanGuard g(st, SQZ_HIP_K_INDEX_SORT);
+    sqzk::launch_index_sort(d_dict, off, 1, a, b, (uint64_t)dict_bytes + 64, st);
+    DictDev dd;
+    dd.bytes = d_dict; dd.len = dict_bytes; dd.sorted = a;
+    return dd;
+}
+// the host flavour: the caller's dictionary into the lane's buffers, indexed when the call encodes
+int upload_dict(Lane& c, hipStream_t st, const uint8_t* dict, uint32_t dict_bytes, bool index, DictDev* dd) {
+    int e;
+    if ((e = c.dict.reserve((size_t)dict_bytes + 16)) || (index && (e = c.dict_idx.reserve(dict_index_bytes(dict_bytes))))) {
+        return e;
+    }
+    HIP_TRY(hipMemcpyAsync(c.dict.p, dict, dict_bytes, hipMemcpyHostToDevice, st));
+    if (index) {
+        *dd = run_dict_index((const uint8_t*)c.dict.p, dict_bytes, (uint8_t*)c.dict_idx.p, st);
+    } else {
+        dd->bytes = (const uint8_t*)c.dict.p; dd->len = dict_bytes; dd->sorted = nullptr;
+    }
+    return 0;
+}
+
 // stage 1 on device buffers -> token words; work = 2 arrays of one uint32 slot per input byte
 // (parse = SQZ_PARSE_LAZY: finder 1 and both work arrays, the callers see to that)
 void run_stage1(int finder, const uint8_t* d_in, const uint64_t* d_in_off, uint32_t n,
                 uint32_t window, uint32_t* tokens, uint32_t* counts,
                 uint32_t* work_a, uint32_t* work_m, uint64_t avg_block, uint64_t slots,
-                hipStream_t st, uint32_t parse = SQZ_PARSE_GREEDY) {
+                hipStream_t st, uint32_t parse = SQZ_PARSE_GREEDY, const DictDev* dd = nullptr) {
     if (finder == 0 || work_a == nullptr || work_m == nullptr) {
         SpanGuard g(st, SQZ_HIP_K_LZ77_SCAN);
         sqzk::launch_lz77_scan(d_in, d_in_off, n, window, tokens, counts, scan_waves(), slots, st);
@@ -333,6 +369,9 @@ void run_stage1(int finder, const uint8_t* d_in, const uint64_t* d_in_off, uint3
         { SpanGuard g(st, SQZ_HIP_K_INDEX_MATCH);
           sqzk::launch_index_match(d_in, d_in_off, n, window, work_a, work_m,
                                    match_groups_for(avg_block), slots, st); }
+        if (dd != nullptr) {                                    // (no slot of sqz_hip_timing is free: not timed here)
+            sqzk::launch_dict_match(d_in, d_in_off, n, window, dd->bytes, dd->len, dd->sorted, work_m, slots, st);
+        }
         { SpanGuard g(st, SQZ_HIP_K_INDEX_PARSE);
           if (parse == SQZ_PARSE_LAZY) {
               sqzk::launch_index_parse_lazy(d_in, d_in_off, n, work_m, tokens, counts, slots, st);
@@ -347,8 +386,9 @@ void run_encode(int finder, const uint8_t* d_in, const uint64_t* d_in_off, uint3
                 uint32_t window, uint32_t* tokens, uint32_t* counts, uint32_t* work_a,
                 uint32_t* work_m, uint64_t avg_block, uint8_t* d_out, const uint64_t* d_out_off,
                 uint64_t* d_out_bytes, int32_t* d_err, uint64_t prefix_acc, int prefix_fill,
-                uint64_t slots, sqz_block_stats* d_stats, hipStream_t st, uint32_t parse = SQZ_PARSE_GREEDY) {
-    run_stage1(finder, d_in, d_in_off, n, window, tokens, counts, work_a, work_m, avg_block, slots, st, parse);
+                uint64_t slots, sqz_block_stats* d_stats, hipStream_t st, uint32_t parse = SQZ_PARSE_GREEDY,
+                const DictDev* dd = nullptr) {
+    run_stage1(finder, d_in, d_in_off, n, window, tokens, counts, work_a, work_m, avg_block, slots, st, parse, dd);
     SpanGuard g(st, SQZ_HIP_K_HUFFMAN_EMIT);
     sqzk::launch_huffman_emit(tokens, d_in_off, counts, d_out, d_out_off, d_out_bytes, d_err, n,
                               prefix_acc, prefix_fill, d_stats, st);
@@ -360,7 +400,7 @@ int encode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_o
                        uint32_t window, uint8_t* out, const uint64_t* out_off,
                        uint64_t* out_bytes, int32_t* err,
                        uint64_t prefix_acc, int prefix_fill, uint64_t* tokens_total,
-                       uint32_t parse = SQZ_PARSE_GREEDY) {
+                       uint32_t parse = SQZ_PARSE_GREEDY, const uint8_t* dict = nullptr, uint32_t dict_bytes = 0) {
     const uint64_t in_base = in_off[0], out_base = out_off[0];
     const uint64_t total_in = in_off[n] - in_base, total_out = out_off[n] - out_base;
     std::vector<uint64_t> io(n + 1), oo(n + 1);
@@ -379,10 +419,13 @@ int encode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_o
     HIP_TRY(hipMemcpyAsync(c.out_off.p, oo.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     uint64_t widest = 0;
     for (uint32_t b = 0; b < n; b++) { widest = io[b + 1] - io[b] > widest ? io[b + 1] - io[b] : widest; }
-    run_encode(finder_for(parse), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, n, window,
+    DictDev dd;
+    if (dict != nullptr && (e = upload_dict(c, st, dict, dict_bytes, true, &dd)) != 0) { return e; }
+    run_encode(dict != nullptr ? 1 : finder_for(parse), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, n, window,
                (uint32_t*)c.work_a.p /* token words take the sorted positions' place */, (uint32_t*)c.tok_count.p,
                (uint32_t*)c.work_a.p, (uint32_t*)c.work_m.p, widest, (uint8_t*)c.out.p, (const uint64_t*)c.out_off.p,
-               (uint64_t*)c.out_bytes.p, (int32_t*)c.err.p, prefix_acc, prefix_fill, total_in + 64, nullptr, st, parse);
+               (uint64_t*)c.out_bytes.p, (int32_t*)c.err.p, prefix_acc, prefix_fill, total_in + 64, nullptr, st, parse,
+               dict != nullptr ? &dd : nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_bytes, c.out_bytes.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(err, c.err.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -426,7 +469,7 @@ int encode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_o
 
 int decode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_off, uint32_t n,
                 uint8_t* out, const uint64_t* out_off, int32_t* err,
-                uint64_t start_bit, uint64_t* end_bit) {
+                uint64_t start_bit, uint64_t* end_bit, const uint8_t* dict = nullptr, uint32_t dict_bytes = 0) {
     const uint64_t in_base = in_off[0], out_base = out_off[0];
     const uint64_t total_in = in_off[n] - in_base, total_out = out_off[n] - out_base;
     std::vector<uint64_t> io(n + 1), oo(n + 1);
@@ -441,17 +484,19 @@ int decode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_o
     if (total_in > 0) { HIP_TRY(hipMemcpyAsync(c.in.p, in + in_base, total_in, hipMemcpyHostToDevice, st)); }
     HIP_TRY(hipMemcpyAsync(c.in_off.p, io.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(c.out_off.p, oo.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    DictDev dd;
+    if (dict != nullptr && (e = upload_dict(c, st, dict, dict_bytes, false, &dd)) != 0) { return e; }
     {
         SpanGuard g(st, SQZ_HIP_K_ENTROPY_DECODE);
         sqzk::launch_entropy_decode((const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p,
                                     (const uint64_t*)c.out_off.p, (uint32_t*)c.tokens.p,
                                     (uint32_t*)c.tok_count.p, (int32_t*)c.err.p,
-                                    (uint64_t*)c.end_bit.p, n, start_bit, decode_waves_for(n), st);
+                                    (uint64_t*)c.end_bit.p, n, start_bit, decode_waves_for(n), st, nullptr, dd.len);
     }
     {
         SpanGuard g(st, SQZ_HIP_K_LZ_EXPAND);
         sqzk::launch_lz_expand((const uint32_t*)c.tokens.p, (const uint32_t*)c.tok_count.p,
-                               (uint8_t*)c.out.p, (const uint64_t*)c.out_off.p, n, st);
+                               (uint8_t*)c.out.p, (const uint64_t*)c.out_off.p, n, st, nullptr, dd.bytes, dd.len);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(err, c.err.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -497,7 +542,8 @@ bool frame_params_ok(uint32_t win_bits, uint32_t block_bits) {
 uint64_t frame_blocks(uint64_t content_bytes, uint32_t block_bits) {
     return (content_bytes >> block_bits) + ((content_bytes & ((1ull << block_bits) - 1)) != 0 ? 1 : 0);
 }
-uint64_t frame_payload_off(uint64_t n_blocks) { return align_up(32 + 8 * n_blocks, 16); }
+// record: the 8 bytes { dict_bytes, dict_crc } behind the index of a version-3 frame, 0 otherwise
+uint64_t frame_payload_off(uint64_t n_blocks, uint64_t record = 0) { return align_up(32 + 8 * n_blocks + record, 16); }
 // content bytes of block b
 uint64_t frame_block_len(uint64_t content_bytes, uint32_t block_bits, uint64_t b) {
     const uint64_t bb = 1ull << block_bits, at = b * bb;
@@ -605,6 +651,26 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
     return hip_errno(hipGetLastError());
 }
 
+// What every frame decode enqueues for n selected blocks once their offsets (and the stored mask, `skip`, null: no
+// block is stored) are on the device: entropy stage, expansion, the stored blocks' copy, the checksums of the output.
+// dd: the shared dictionary of a version-3 frame (len 0: none).  Shared by the device-resident decode, whose offsets
+// frame_open_kernel wrote, and the host decode of a version-3 frame, whose offsets the host worked out.
+void run_frame_decode(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* out_off, uint32_t n,
+                      uint64_t size_hint, uint32_t* tokens, uint32_t* counts, uint8_t* d_out, int32_t* d_err,
+                      const uint32_t* skip, const uint32_t* stored, uint32_t* crc, const DictDev& dd, hipStream_t st) {
+    { SpanGuard g(st, SQZ_HIP_K_ENTROPY_DECODE);
+      sqzk::launch_entropy_decode(d_in, in_off, out_off, tokens, counts, d_err, nullptr, n, 0, decode_waves_for(n), st,
+                                  skip, dd.len); }
+    { SpanGuard g(st, SQZ_HIP_K_LZ_EXPAND);
+      sqzk::launch_lz_expand(tokens, counts, d_out, out_off, n, st, skip, dd.bytes, dd.len); }
+    if (skip != nullptr) {                                  // a stored block ignores the dictionary
+        SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+        sqzk::launch_range_copy(d_in, in_off, d_out, out_off, out_off, stored, n, false, size_hint, st);
+    }
+    { SpanGuard g(st, SQZ_HIP_K_CRC32);
+      sqzk::launch_crc32_blocks(d_out, out_off, n, crc, size_hint, st); }
+}
+
 // the device side of a frame decode, blocks [first, first + n_sel) into d_out (block `first` at its start)
 int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_t content_bytes, uint32_t first,
                      uint32_t n_sel, uint64_t sel_bytes, uint8_t* d_out, int32_t* d_err, int32_t* d_status,
@@ -631,18 +697,8 @@ int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_
     if (n_sel > 0) {
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + align_up((uint64_t)n_sel * 4, 256));
-        { SpanGuard g(st, SQZ_HIP_K_ENTROPY_DECODE);
-          sqzk::launch_entropy_decode(d_frame, in_off, out_off, tokens, counts, d_err, nullptr, n_sel, 0,
-                                      decode_waves_for(n_sel), st, skip); }
-        { SpanGuard g(st, SQZ_HIP_K_LZ_EXPAND);
-          sqzk::launch_lz_expand(tokens, counts, d_out, out_off, n_sel, st, skip); }
-        if (skip != nullptr) {
-            SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
-            sqzk::launch_range_copy(d_frame, in_off, d_out, out_off, out_off, stored, n_sel, false,
-                                    (sel_bytes + n_sel - 1) / n_sel, st);
-        }
-        { SpanGuard g(st, SQZ_HIP_K_CRC32);
-          sqzk::launch_crc32_blocks(d_out, out_off, n_sel, crc, (sel_bytes + n_sel - 1) / n_sel, st); }
+        run_frame_decode(d_frame, in_off, out_off, n_sel, (sel_bytes + n_sel - 1) / n_sel, tokens, counts, d_out, d_err,
+                         skip, stored, crc, DictDev(), st);
         sqzk::launch_frame_verify(d_frame, first, n_sel, crc, d_status, d_err, st);
     }
     return hip_errno(hipGetLastError());
@@ -683,6 +739,63 @@ int frame_decode_host(Lane& c, hipStream_t st, const uint8_t* frame, const struc
         HIP_TRY(hipMemcpyAsync(&status, c.misc.p, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (status != 0) { return status; }
+        if ((e = sink(p0, pn, errs.data(), (const uint8_t*)c.out.p, c1 - c0)) != 0) { return e; }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+// Host flavour of decode for a version-3 frame (shared dictionary).  The host has checked header, index and
+// record (sqz_frame_info), so the offsets and the stored mask of a pass are worked out here and uploaded with its
+// streams, and the checksums come back to be compared here: the device-resident decode's open kernel, which
+// refuses version 3, is not involved.  Same passes and the same sink as frame_decode_host, and the same kernels
+// behind the offsets (run_frame_decode); what differs is where the offsets come from and where the checksums are
+// compared, which is what version 3 in the device-resident flavour will fold back into one.
+template <class Sink>
+int frame_decode_host_dict(Lane& c, hipStream_t st, const uint8_t* frame, const struct sqz_frame_info& fi,
+                           uint64_t b_first, uint64_t b_end, const DictDev& dd, Sink sink) {
+    const uint64_t bb = fi.block_bytes, n = fi.n_blocks;
+    std::vector<uint64_t> pre(n + 1);
+    pre[0] = 0;
+    for (uint64_t b = 0; b < n; b++) { pre[b + 1] = pre[b] + 8 * (uint64_t)frame_entry_words(frame, fi.version, b); }
+    const uint64_t pass = frame_pass_blocks(bb);
+    std::vector<uint64_t> io, oo;
+    std::vector<uint32_t> mask, crc;
+    std::vector<int32_t> errs;
+    int e;
+    for (uint64_t p0 = b_first; p0 < b_end; p0 += pass) {
+        const uint64_t pn = b_end - p0 < pass ? b_end - p0 : pass;
+        const uint64_t c0 = p0 * bb, c1 = (p0 + pn) * bb < fi.content_bytes ? (p0 + pn) * bb : fi.content_bytes;
+        const uint64_t in_bytes = pre[p0 + pn] - pre[p0];
+        io.resize(pn + 1); oo.resize(pn + 1); mask.resize(pn); crc.resize(pn); errs.resize(pn);
+        bool any_stored = false;
+        for (uint64_t k = 0; k <= pn; k++) {
+            io[k] = pre[p0 + k] - pre[p0];
+            oo[k] = ((p0 + k) * bb < fi.content_bytes ? (p0 + k) * bb : fi.content_bytes) - c0;
+            if (k < pn) { mask[k] = frame_entry_stored(frame, fi.version, p0 + k) ? 1u : 0u; any_stored |= mask[k] != 0; }
+        }
+        if ((e = c.in.reserve(in_bytes + 16)) || (e = c.out.reserve(c1 - c0 + 16)) ||
+            (e = c.in_off.reserve((pn + 1) * 8)) || (e = c.out_off.reserve((pn + 1) * 8)) ||
+            (e = c.mask.reserve(pn * 4 + 4)) || (e = c.crc.reserve(pn * 4 + 4)) || (e = c.err.reserve(pn * 4)) ||
+            (e = c.tokens.reserve((c1 - c0 + 64) * 4)) || (e = c.tok_count.reserve(pn * 4))) { return e; }
+        if (in_bytes > 0) {
+            HIP_TRY(hipMemcpyAsync(c.in.p, frame + fi.payload_off + pre[p0], in_bytes, hipMemcpyHostToDevice, st));
+        }
+        HIP_TRY(hipMemcpyAsync(c.in_off.p, io.data(), (pn + 1) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c.out_off.p, oo.data(), (pn + 1) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c.mask.p, mask.data(), pn * 4, hipMemcpyHostToDevice, st));
+        const uint32_t* const skip = any_stored ? (const uint32_t*)c.mask.p : nullptr;
+        const uint64_t hint = (c1 - c0 + pn - 1) / pn;
+        run_frame_decode((const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, (const uint64_t*)c.out_off.p, (uint32_t)pn,
+                         hint, (uint32_t*)c.tokens.p, (uint32_t*)c.tok_count.p, (uint8_t*)c.out.p, (int32_t*)c.err.p,
+                         skip, skip, (uint32_t*)c.crc.p, dd, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(errs.data(), c.err.p, pn * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(crc.data(), c.crc.p, pn * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint64_t k = 0; k < pn; k++) {
+            if (errs[k] == 0 && crc[k] != get_le32(frame + 32 + 8 * (p0 + k) + 4)) { errs[k] = EILSEQ; }
+        }
         if ((e = sink(p0, pn, errs.data(), (const uint8_t*)c.out.p, c1 - c0)) != 0) { return e; }
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -983,7 +1096,40 @@ int sqz_decode_blocks(const uint8_t* in, const uint64_t* in_off, uint32_t n,
     return decode_host(*lease.lane, lease.stream(nullptr), in, in_off, n, out, out_off, err, 0, nullptr);
 }
 
+int sqz_encode_blocks_dict(const uint8_t* in, const uint64_t* in_off, uint32_t n, uint32_t window, uint32_t parse,
+                           const uint8_t* dict, uint64_t dict_bytes, uint8_t* out, const uint64_t* out_off,
+                           uint64_t* out_bytes, int32_t* err) {
+    if (!parse_ok(parse) || !window_ok(window) || !dict_ok(dict, dict_bytes, window)) { return EINVAL; }
+    if (n == 0) { return 0; }
+    if (in_off == NULL || out_off == NULL || out == NULL || out_bytes == NULL || err == NULL) { return EINVAL; }
+    if (check_offsets(in_off, n, false) != 0 || check_offsets(out_off, n, true) != 0) { return EINVAL; }
+    if (in == NULL && in_off[n] != in_off[0]) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    LaneLease lease;
+    return encode_host(*lease.lane, lease.stream(nullptr), in, in_off, n, window, out, out_off, out_bytes, err,
+                       0, 0, nullptr, parse, dict, (uint32_t)dict_bytes);
+}
+
+int sqz_decode_blocks_dict(const uint8_t* in, const uint64_t* in_off, uint32_t n, const uint8_t* dict,
+                           uint64_t dict_bytes, uint8_t* out, const uint64_t* out_off, int32_t* err) {
+    if (!dict_ok(dict, dict_bytes, (uint32_t)sqzk_max_window)) { return EINVAL; }
+    if (n == 0) { return 0; }
+    if (in == NULL || in_off == NULL || out_off == NULL || err == NULL) { return EINVAL; }
+    if (check_offsets(in_off, n, true) != 0 || check_offsets(out_off, n, false) != 0) { return EINVAL; }
+    if (out == NULL && out_off[n] != out_off[0]) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    LaneLease lease;
+    return decode_host(*lease.lane, lease.stream(nullptr), in, in_off, n, out, out_off, err, 0, nullptr, dict,
+                       (uint32_t)dict_bytes);
+}
+
 // ------------------------------------------------------------------ batch, device
+uint64_t sqz_hip_encode_scratch_bytes_dict(uint32_t n, uint64_t total_in_bytes, uint64_t dict_bytes) {
+    return dict_index_bytes(dict_bytes) + sqz_hip_encode_scratch_bytes(n, total_in_bytes);
+}
+
 uint64_t sqz_hip_encode_scratch_bytes(uint32_t n, uint64_t total_in_bytes) {
     // token counts + two uint32 slots per input byte: sorted positions, later the token words / the sort's
     // second buffer, later the match table
@@ -1027,6 +1173,25 @@ int sqz_hip_lz77_blocks_parse(const void* d_in, const uint64_t* d_in_off, uint32
     run_stage1(finder, (const uint8_t*)d_in, d_in_off, n, window, d_tokens, d_token_count,
                finder == 1 ? wa : nullptr, finder == 1 ? wm : nullptr,
                slots / (n > 0 ? n : 1), finder == 1 ? slots : ~0ull, (hipStream_t)stream, parse);
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_lz77_blocks_dict(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window,
+                             uint32_t* d_tokens, uint32_t* d_token_count, int finder, uint32_t parse,
+                             const void* d_dict, uint64_t dict_bytes, void* d_work, uint64_t work_bytes, void* stream) {
+    // the scan finder has no match table to merge into
+    if (!parse_ok(parse) || finder != 1 || !window_ok(window) || !dict_ok(d_dict, dict_bytes, window)) { return EINVAL; }
+    const uint64_t head = dict_index_bytes(dict_bytes);
+    if (d_work == NULL || ((uintptr_t)d_work & 15u) != 0 || work_bytes < head + 8 * 64) { return EINVAL; }
+    if (n == 0) { return 0; }
+    if (d_in == NULL || d_in_off == NULL || d_tokens == NULL || d_token_count == NULL) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    const DictDev dd = run_dict_index((const uint8_t*)d_dict, (uint32_t)dict_bytes, (uint8_t*)d_work, (hipStream_t)stream);
+    const uint64_t slots = (work_bytes - head) / 8;
+    uint32_t* wa = (uint32_t*)((uint8_t*)d_work + head);
+    run_stage1(1, (const uint8_t*)d_in, d_in_off, n, window, d_tokens, d_token_count, wa, wa + slots,
+               slots / n, slots, (hipStream_t)stream, parse, &dd);
     return hip_errno(hipGetLastError());
 }
 
@@ -1107,6 +1272,53 @@ static int encode_blocks_dev(const void* d_in, const uint64_t* d_in_off, uint32_
     run_encode(finder_for(parse), (const uint8_t*)d_in, d_in_off, n, window, tokens, counts,
                work_a, work_m, slots / n, (uint8_t*)d_out, d_out_off, d_out_bytes, d_err, 0, 0,
                slots, d_stats, (hipStream_t)stream, parse);
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_encode_blocks_dict(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t window, uint32_t parse,
+                               const void* d_dict, uint64_t dict_bytes, void* d_out, const uint64_t* d_out_off,
+                               uint64_t* d_out_bytes, int32_t* d_err, void* d_scratch, uint64_t scratch_bytes,
+                               void* stream) {
+    if (!parse_ok(parse) || !window_ok(window) || !dict_ok(d_dict, dict_bytes, window)) { return EINVAL; }
+    if (d_scratch == NULL || ((uintptr_t)d_scratch & 15u) != 0 ||
+        scratch_bytes < sqz_hip_encode_scratch_bytes_dict(n, 0, dict_bytes)) { return EINVAL; }
+    if (n == 0) { return 0; }
+    if (d_in == NULL || d_in_off == NULL || d_out == NULL || d_out_off == NULL || d_out_bytes == NULL ||
+        d_err == NULL) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    // the dictionary's index first, then the scratch of sqz_hip_encode_blocks
+    const uint64_t idx = dict_index_bytes(dict_bytes);
+    const DictDev dd = run_dict_index((const uint8_t*)d_dict, (uint32_t)dict_bytes, (uint8_t*)d_scratch, (hipStream_t)stream);
+    uint8_t* const rest = (uint8_t*)d_scratch + idx;
+    const uint64_t head = align_up((uint64_t)n * 4, 256);
+    const uint64_t slots = (scratch_bytes - idx - head) / 8;
+    uint32_t* counts = (uint32_t*)rest;
+    uint32_t* tokens = (uint32_t*)(rest + head);
+    run_encode(1, (const uint8_t*)d_in, d_in_off, n, window, tokens, counts, tokens, tokens + slots, slots / n,
+               (uint8_t*)d_out, d_out_off, d_out_bytes, d_err, 0, 0, slots, nullptr, (hipStream_t)stream, parse, &dd);
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_decode_blocks_dict(const void* d_in, const uint64_t* d_in_off, uint32_t n, const void* d_dict,
+                               uint64_t dict_bytes, void* d_out, const uint64_t* d_out_off, int32_t* d_err,
+                               void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!dict_ok(d_dict, dict_bytes, (uint32_t)sqzk_max_window)) { return EINVAL; }
+    if (n == 0) { return 0; }
+    if (d_in == NULL || d_in_off == NULL || d_out == NULL || d_out_off == NULL || d_err == NULL ||
+        d_scratch == NULL || scratch_bytes < sqz_hip_decode_scratch_bytes(n, 0)) {
+        return EINVAL;
+    }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    uint32_t* counts = (uint32_t*)d_scratch;
+    uint32_t* tokens = (uint32_t*)((uint8_t*)d_scratch + align_up((uint64_t)n * 4, 256));
+    { SpanGuard g((hipStream_t)stream, SQZ_HIP_K_ENTROPY_DECODE);
+      sqzk::launch_entropy_decode((const uint8_t*)d_in, d_in_off, d_out_off, tokens, counts, d_err,
+                                  nullptr, n, 0, decode_waves_for(n), (hipStream_t)stream, nullptr, (uint32_t)dict_bytes); }
+    { SpanGuard g((hipStream_t)stream, SQZ_HIP_K_LZ_EXPAND);
+      sqzk::launch_lz_expand(tokens, counts, (uint8_t*)d_out, d_out_off, n, (hipStream_t)stream, nullptr,
+                             (const uint8_t*)d_dict, (uint32_t)dict_bytes); }
     return hip_errno(hipGetLastError());
 }
 
@@ -1295,14 +1507,17 @@ int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* 
     if (frame == NULL || out == NULL) { return EINVAL; }
     if (avail < 32) { return E2BIG; }
     const uint32_t win_bits = frame[5], block_bits = frame[6];
-    // version 1 has no flags; version 2 has at least one, and only known ones
+    // version 1 has no flags; version 2 has at least one, and only known ones; version 3 iff SQZ_FRAME_DICT
     const uint32_t version = frame[4], flags = frame[7];
-    const bool version_ok = (version == 1 && flags == 0) || (version == 2 && flags == (uint32_t)SQZ_FRAME_STORED);
+    const bool version_ok = (version == 1 && flags == 0) || (version == 2 && flags == (uint32_t)SQZ_FRAME_STORED) ||
+                            (version == 3 && (flags & (uint32_t)SQZ_FRAME_DICT) != 0 &&
+                             (flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_DICT)) == 0);
+    const uint64_t record = version == 3 ? 8 : 0;           // { dict_bytes, dict_crc } behind the index
     if (get_le32(frame) != 0x465A5153u || !version_ok || !frame_params_ok(win_bits, block_bits)) { return EINVAL; }
     const uint64_t content = get_le64(frame + 8), payload = get_le64(frame + 16);
     const uint64_t n = get_le32(frame + 24);
     if (frame_blocks(content, block_bits) != n || (payload & 7u) != 0) { return EINVAL; }
-    const uint64_t payload_off = frame_payload_off(n);      // n < 2^32: no overflow
+    const uint64_t payload_off = frame_payload_off(n, record);      // n < 2^32: no overflow
     if (payload > ~(uint64_t)0 - payload_off) { return EINVAL; }
     out->content_bytes = content;
     out->payload_bytes = payload;
@@ -1313,14 +1528,19 @@ int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* 
     out->win_bits = win_bits;
     out->version = version;
     out->reserved = flags;
-    if (avail >= 32 + 8 * n) {                              // the index is there: check it too
-        const uint32_t crc = host_crc32(host_crc32(0, frame, 28), frame + 32, 8 * n);
+    if (avail >= 32 + 8 * n + record) {                     // the index (and the record) is there: check it too
+        const uint32_t crc = host_crc32(host_crc32(0, frame, 28), frame + 32, 8 * n + record);
         if (crc != get_le32(frame + 28)) { return EILSEQ; }
+        if (version == 3) {                                 // a dictionary of 1 .. window - 1 bytes
+            const uint32_t db = get_le32(frame + 32 + 8 * n);
+            if (db == 0 || db > (1u << win_bits) - 1u) { return EINVAL; }
+        }
         uint64_t words = 0;
         for (uint64_t b = 0; b < n; b++) {                  // < 2^64: n, words < 2^32
             const uint32_t w = frame_entry_words(frame, version, b);
             if (frame_entry_stored(frame, version, b) &&
-                w != (frame_block_len(content, block_bits, b) + 7) / 8) { return EINVAL; }
+                ((flags & (uint32_t)SQZ_FRAME_STORED) == 0 ||
+                 w != (frame_block_len(content, block_bits, b) + 7) / 8)) { return EINVAL; }
             words += w;
         }
         if (words != payload / 8) { return EINVAL; }
@@ -1359,6 +1579,25 @@ uint64_t sqz_frame_bound_ex(uint64_t content_bytes, uint32_t block_bits, uint32_
     return frame_payload_off(frame_blocks(content_bytes, block_bits)) + align_up(content_bytes, 8);
 }
 
+uint64_t sqz_frame_bound_dict(uint64_t content_bytes, uint32_t block_bits, uint32_t flags) {
+    if ((flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_DICT)) != 0) { return 0; }
+    const uint64_t plain = sqz_frame_bound_ex(content_bytes, block_bits, flags & (uint32_t)SQZ_FRAME_STORED);
+    if (plain == 0) { return 0; }
+    const uint64_t n = frame_blocks(content_bytes, block_bits);      // the record: 8 bytes more in front of the padding
+    return plain - frame_payload_off(n) + frame_payload_off(n, 8);
+}
+
+int sqz_frame_dict(const uint8_t* frame, uint64_t avail, uint32_t* dict_bytes, uint32_t* dict_crc) {
+    struct sqz_frame_info fi;
+    const int e = frame_check_host(frame, avail, &fi);
+    if (e != 0) { return e; }
+    if (fi.version != 3) { return EINVAL; }
+    const uint8_t* const rec = frame + 32 + 8 * (uint64_t)fi.n_blocks;
+    if (dict_bytes != NULL) { *dict_bytes = get_le32(rec); }
+    if (dict_crc != NULL) { *dict_crc = get_le32(rec + 4); }
+    return 0;
+}
+
 int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
                        uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
     return sqz_frame_compress_ex(data, bytes, win_bits, block_bits, 0, frame, capacity, frame_bytes);
@@ -1370,16 +1609,37 @@ int sqz_frame_compress_ex(const uint8_t* data, uint64_t bytes, uint32_t win_bits
                                     frame_bytes);
 }
 
+static int frame_compress_host(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                               uint32_t flags, uint32_t parse, const uint8_t* dict, uint32_t dict_bytes,
+                               uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes);
+
 int sqz_frame_compress_parse(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
                              uint32_t flags, uint32_t parse, uint8_t* frame, uint64_t capacity,
                              uint64_t* frame_bytes) {
+    return frame_compress_host(data, bytes, win_bits, block_bits, flags, parse, NULL, 0, frame, capacity, frame_bytes);
+}
+
+int sqz_frame_compress_dict(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                            uint32_t flags, uint32_t parse, const uint8_t* dict, uint64_t dict_bytes,
+                            uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
+    if ((flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_DICT)) != 0 || !frame_params_ok(win_bits, block_bits) ||
+        !dict_ok(dict, dict_bytes, 1u << win_bits)) { return EINVAL; }
+    return frame_compress_host(data, bytes, win_bits, block_bits, flags & (uint32_t)SQZ_FRAME_STORED, parse, dict,
+                               (uint32_t)dict_bytes, frame, capacity, frame_bytes);
+}
+
+// dict == NULL: versions 1 and 2 as they always were; else version 3, flags | SQZ_FRAME_DICT
+static int frame_compress_host(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                               uint32_t flags, uint32_t parse, const uint8_t* dict, uint32_t dict_bytes,
+                               uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
     if (!parse_ok(parse)) { return EINVAL; }
     if (frame_bytes == NULL || (frame == NULL && capacity > 0) || (data == NULL && bytes > 0) ||
         !frame_params_ok(win_bits, block_bits) || !frame_flags_ok(flags)) { return EINVAL; }
     const bool store = (flags & SQZ_FRAME_STORED) != 0;
     const uint64_t bb = 1ull << block_bits, n = frame_blocks(bytes, block_bits);
     if (n > 0xFFFFFFFFull) { return EINVAL; }
-    const uint64_t payload_off = frame_payload_off(n), slab = sqz_bound(bb);
+    const uint64_t record = dict != NULL ? 8 : 0;
+    const uint64_t payload_off = frame_payload_off(n, record), slab = sqz_bound(bb);
     bool fits = capacity >= payload_off;
     std::vector<uint8_t> head(payload_off, 0);              // header, index, padding: built here, copied at the end
     uint64_t payload = 0;
@@ -1393,6 +1653,8 @@ int sqz_frame_compress_parse(const uint8_t* data, uint64_t bytes, uint32_t win_b
         std::vector<uint64_t> out_bytes, dense_off;
         std::vector<int32_t> err;
         std::vector<uint32_t> crc;
+        DictDev dd;                                         // uploaded and indexed once, whatever the number of passes
+        if (dict != NULL && (e = upload_dict(c, st, dict, dict_bytes, true, &dd)) != 0) { return e; }
         for (uint64_t p0 = 0; p0 < n; p0 += pass) {
             const uint32_t pn = (uint32_t)(n - p0 < pass ? n - p0 : pass);
             const uint64_t c0 = p0 * bb, c1 = (p0 + pn) * bb < bytes ? (p0 + pn) * bb : bytes, total_in = c1 - c0;
@@ -1405,10 +1667,11 @@ int sqz_frame_compress_parse(const uint8_t* data, uint64_t bytes, uint32_t win_b
             sqzk::launch_frame_plan(pn, bb, total_in, slab, (uint64_t*)c.in_off.p, (uint64_t*)c.out_off.p, st);
             { SpanGuard g(st, SQZ_HIP_K_CRC32);
               sqzk::launch_crc32_blocks((const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, (uint32_t*)c.crc.p, bb, st); }
-            run_encode(finder_for(parse), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, 1u << win_bits,
+            run_encode(dict != NULL ? 1 : finder_for(parse), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn,
+                       1u << win_bits,
                        (uint32_t*)c.work_a.p, (uint32_t*)c.tok_count.p, (uint32_t*)c.work_a.p, (uint32_t*)c.work_m.p, bb,
                        (uint8_t*)c.out.p, (const uint64_t*)c.out_off.p, (uint64_t*)c.out_bytes.p, (int32_t*)c.err.p,
-                       0, 0, total_in + 64, nullptr, st, parse);
+                       0, 0, total_in + 64, nullptr, st, parse, dict != NULL ? &dd : nullptr);
             HIP_TRY(hipGetLastError());
             out_bytes.resize(pn); err.resize(pn); crc.resize(pn); dense_off.resize((size_t)pn + 1);
             HIP_TRY(hipMemcpyAsync(out_bytes.data(), c.out_bytes.p, (size_t)pn * 8, hipMemcpyDeviceToHost, st));
@@ -1456,11 +1719,16 @@ int sqz_frame_compress_parse(const uint8_t* data, uint64_t bytes, uint32_t win_b
     if (!fits) { return E2BIG; }
     uint8_t* h = head.data();
     put_le32(h, 0x465A5153u);
-    h[4] = store ? 2 : 1; h[5] = (uint8_t)win_bits; h[6] = (uint8_t)block_bits; h[7] = (uint8_t)flags;
+    h[4] = dict != NULL ? 3 : store ? 2 : 1; h[5] = (uint8_t)win_bits; h[6] = (uint8_t)block_bits;
+    h[7] = (uint8_t)(flags | (dict != NULL ? (uint32_t)SQZ_FRAME_DICT : 0u));
     put_le64(h + 8, bytes);
     put_le64(h + 16, payload);
     put_le32(h + 24, (uint32_t)n);
-    put_le32(h + 28, host_crc32(host_crc32(0, h, 28), h + 32, 8 * n));
+    if (dict != NULL) {                                     // the record: which dictionary a reader has to bring
+        put_le32(h + 32 + 8 * n, dict_bytes);
+        put_le32(h + 32 + 8 * n + 4, host_crc32(0, dict, dict_bytes));
+    }
+    put_le32(h + 28, host_crc32(host_crc32(0, h, 28), h + 32, 8 * n + record));
     memcpy(frame, h, payload_off);
     return 0;
 }
@@ -1470,6 +1738,7 @@ int sqz_frame_decompress(const uint8_t* frame, uint64_t avail, uint8_t* data, ui
     struct sqz_frame_info fi;
     int e = frame_check_host(frame, avail, &fi);
     if (e != 0) { return e; }
+    if (fi.version == 3) { return EINVAL; }                 // needs its dictionary: sqz_frame_decompress_dict
     if (bytes != NULL) { *bytes = fi.content_bytes; }
     if (avail < fi.frame_bytes || capacity < fi.content_bytes) { return E2BIG; }
     if (fi.n_blocks == 0) { return 0; }
@@ -1496,6 +1765,7 @@ int sqz_frame_read(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64
     struct sqz_frame_info fi;
     int e = frame_check_host(frame, avail, &fi);
     if (e != 0) { return e; }
+    if (fi.version == 3) { return EINVAL; }                 // needs its dictionary: sqz_frame_read_dict
     if (offset > fi.content_bytes || length > fi.content_bytes - offset || (out == NULL && length > 0)) { return EINVAL; }
     if (length == 0) { return 0; }
     const uint64_t bb = fi.block_bytes, b_first = offset / bb, b_end = (offset + length - 1) / bb + 1;
@@ -1506,6 +1776,77 @@ int sqz_frame_read(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64
     LaneLease lease;
     hipStream_t st = lease.stream(nullptr);
     return frame_decode_host(*lease.lane, st, frame, fi, b_first, b_end,
+        [&](uint64_t p0, uint64_t pn, const int32_t* errs, const uint8_t* d_bytes, uint64_t count) -> int {
+            for (uint64_t k = 0; k < pn; k++) { if (errs[k] != 0) { return errs[k]; } }
+            const uint64_t lo = offset > p0 * bb ? offset : p0 * bb;
+            const uint64_t hi = offset + length < p0 * bb + count ? offset + length : p0 * bb + count;
+            if (hi > lo) {
+                HIP_TRY(hipMemcpyAsync(out + (lo - offset), d_bytes + (lo - p0 * bb), hi - lo, hipMemcpyDeviceToHost, st));
+            }
+            return 0;
+        });
+}
+
+// a version-3 frame and the dictionary a reader brought: EINVAL a frame of another version or an impossible
+// dictionary, EILSEQ one that is not the writer's (length or checksum)
+static int frame_dict_check(const uint8_t* frame, const struct sqz_frame_info& fi, const uint8_t* dict, uint64_t dict_bytes) {
+    if (fi.version != 3 || !dict_ok(dict, dict_bytes, 1u << fi.win_bits)) { return EINVAL; }
+    const uint8_t* const rec = frame + 32 + 8 * (uint64_t)fi.n_blocks;
+    if (get_le32(rec) != dict_bytes || get_le32(rec + 4) != host_crc32(0, dict, dict_bytes)) { return EILSEQ; }
+    return 0;
+}
+
+int sqz_frame_decompress_dict(const uint8_t* frame, uint64_t avail, const uint8_t* dict, uint64_t dict_bytes,
+                              uint8_t* data, uint64_t capacity, uint64_t* bytes, int32_t* block_err) {
+    struct sqz_frame_info fi;
+    int e = frame_check_host(frame, avail, &fi);
+    if (e != 0) { return e; }
+    if ((e = frame_dict_check(frame, fi, dict, dict_bytes)) != 0) {
+        if (e == EILSEQ && block_err != NULL) { for (uint32_t b = 0; b < fi.n_blocks; b++) { block_err[b] = EILSEQ; } }
+        return e;
+    }
+    if (bytes != NULL) { *bytes = fi.content_bytes; }
+    if (avail < fi.frame_bytes || capacity < fi.content_bytes) { return E2BIG; }
+    if (fi.n_blocks == 0) { return 0; }
+    if (data == NULL) { return EINVAL; }
+    if ((e = device_ready()) != 0) { return e; }
+    LaneLease lease;
+    hipStream_t st = lease.stream(nullptr);
+    DictDev dd;
+    if ((e = upload_dict(*lease.lane, st, dict, (uint32_t)dict_bytes, false, &dd)) != 0) { return e; }
+    int first_bad = 0;
+    e = frame_decode_host_dict(*lease.lane, st, frame, fi, 0, fi.n_blocks, dd,
+        [&](uint64_t p0, uint64_t pn, const int32_t* errs, const uint8_t* d_bytes, uint64_t count) -> int {
+            for (uint64_t k = 0; k < pn; k++) {
+                if (block_err != NULL) { block_err[p0 + k] = errs[k]; }
+                if (first_bad == 0) { first_bad = errs[k]; }
+            }
+            if (count > 0) {
+                HIP_TRY(hipMemcpyAsync(data + p0 * fi.block_bytes, d_bytes, count, hipMemcpyDeviceToHost, st));
+            }
+            return 0;
+        });
+    return e != 0 ? e : first_bad;
+}
+
+int sqz_frame_read_dict(const uint8_t* frame, uint64_t avail, const uint8_t* dict, uint64_t dict_bytes,
+                        uint64_t offset, uint64_t length, uint8_t* out) {
+    struct sqz_frame_info fi;
+    int e = frame_check_host(frame, avail, &fi);
+    if (e != 0) { return e; }
+    if ((e = frame_dict_check(frame, fi, dict, dict_bytes)) != 0) { return e; }
+    if (offset > fi.content_bytes || length > fi.content_bytes - offset || (out == NULL && length > 0)) { return EINVAL; }
+    if (length == 0) { return 0; }
+    const uint64_t bb = fi.block_bytes, b_first = offset / bb, b_end = (offset + length - 1) / bb + 1;
+    uint64_t words = 0;                                     // the covering streams must be inside avail
+    for (uint64_t b = 0; b < b_end; b++) { words += frame_entry_words(frame, fi.version, b); }
+    if (8 * words > avail - fi.payload_off) { return E2BIG; }
+    if ((e = device_ready()) != 0) { return e; }
+    LaneLease lease;
+    hipStream_t st = lease.stream(nullptr);
+    DictDev dd;
+    if ((e = upload_dict(*lease.lane, st, dict, (uint32_t)dict_bytes, false, &dd)) != 0) { return e; }
+    return frame_decode_host_dict(*lease.lane, st, frame, fi, b_first, b_end, dd,
         [&](uint64_t p0, uint64_t pn, const int32_t* errs, const uint8_t* d_bytes, uint64_t count) -> int {
             for (uint64_t k = 0; k < pn; k++) { if (errs[k] != 0) { return errs[k]; } }
             const uint64_t lo = offset > p0 * bb ? offset : p0 * bb;

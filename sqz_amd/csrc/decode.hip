@@ -101,7 +101,11 @@ __device__ __forceinline__ int peek_symbol(BitSource& r, const T& t) {
 // from its own bit position), so errors and updates are the reference's.
 // kSkip: the instantiation that looks at `skip` (SQZF stored blocks).  Without it the kernel is, instruction for
 // instruction, the one that never had the argument: a batch without a mask pays nothing for the feature.
-template <bool kSkip>
+// kHist: the instantiation that looks at `history` (a shared dictionary in front of every block).  Without it the
+// argument is not read and the checks are the ones that never had it: measured, an `i + history` in the checks of
+// the plain instantiation moved its register allocation and cost the 4096-block decode step 1.3 ms of 83
+// (profiles/dict_decode_ab.json; DESIGN.md section 10, "The existing path").
+template <bool kSkip, bool kHist>
 __global__ __launch_bounds__(kWave, 4)          // four waves per SIMD: 16 streams per CU (the LDS allows as many)
 void entropy_decode_kernel(const uint8_t* __restrict__ in,
                            const uint64_t* __restrict__ in_off,
@@ -112,7 +116,8 @@ void entropy_decode_kernel(const uint8_t* __restrict__ in,
                            uint64_t* __restrict__ end_bit,   // optional: bit position after the last symbol
                            uint32_t n_blocks,
                            uint64_t start_bit,
-                           const uint32_t* __restrict__ skip) {   // optional: blocks that are not streams (SQZF stored blocks)
+                           const uint32_t* __restrict__ skip,    // optional: blocks that are not streams (SQZF stored blocks)
+                           uint32_t history) {                    // bytes in front of every block a distance may reach into (a shared dictionary; 0: none)
     __shared__ DecodeLds lds;
     const int lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
@@ -192,7 +197,7 @@ void entropy_decode_kernel(const uint8_t* __restrict__ in,
                 if (r.overrun()) { err = kE2BIG; return; }
             }
             // squeeze.h:534-541: 0 < pos <= 0x7FFF (code 29 with all 13 extra bits set is 32768)
-            if (dist > 0x7FFF || (uint64_t)dist > i || (uint64_t)len > bytes - i) { err = kEINVAL; return; }
+            if (dist > 0x7FFF || (uint64_t)dist > i + (kHist ? history : 0u) || (uint64_t)len > bytes - i) { err = kEINVAL; return; }
             word = kTokMatch | ((uint32_t)len << 16) | (uint32_t)dist;
             i += (uint64_t)len;
         }
@@ -373,7 +378,7 @@ void entropy_decode_kernel(const uint8_t* __restrict__ in,
         const uint64_t out_before = i + (uint64_t)((scan & 0xFFFFu) - tlen_v);
         const bool invalid = lane < m &&
             (out_before >= bytes ||
-             (is_match && ((uint64_t)(word_v & 0x7FFFu) > out_before || (uint64_t)tlen_v > bytes - out_before)));
+             (is_match && ((uint64_t)(word_v & 0x7FFFu) > out_before + (kHist ? history : 0u) || (uint64_t)tlen_v > bytes - out_before)));
         const uint64_t inv = __ballot(invalid);
         if (inv != 0) { const int f = __builtin_ctzll(inv); if (f < m) { m = f; stop = true; } }
         int a_v = -1, b_v = -1;
@@ -543,7 +548,7 @@ struct DecodeMwLds {
     MwRound    round[2];
 };
 
-template <int W, bool kSkip>
+template <int W, bool kSkip, bool kHist>
 __global__ __launch_bounds__(kWave * W, 4)      // 128 VGPRs: 16 waves per CU = 16 / W streams
 void entropy_decode_mw_kernel(const uint8_t* __restrict__ in,
                               const uint64_t* __restrict__ in_off,
@@ -554,7 +559,8 @@ void entropy_decode_mw_kernel(const uint8_t* __restrict__ in,
                               uint64_t* __restrict__ end_bit,
                               uint32_t n_blocks,
                               uint64_t start_bit,
-                              const uint32_t* __restrict__ skip) {
+                              const uint32_t* __restrict__ skip,
+                              uint32_t history) {                 // as in entropy_decode_kernel
     __shared__ DecodeMwLds<W> lds;
     const int lane = (int)(threadIdx.x & (kWave - 1));
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -634,7 +640,7 @@ void entropy_decode_mw_kernel(const uint8_t* __restrict__ in,
                 dist += (int)r.get_lsb(xb);
                 if (r.overrun()) { err = kE2BIG; return; }
             }
-            if (dist > 0x7FFF || (uint64_t)dist > i || (uint64_t)len > bytes - i) { err = kEINVAL; return; }
+            if (dist > 0x7FFF || (uint64_t)dist > i + (kHist ? history : 0u) || (uint64_t)len > bytes - i) { err = kEINVAL; return; }
             word = kTokMatch | ((uint32_t)len << 16) | (uint32_t)dist;
             i += (uint64_t)len;
         }
@@ -908,7 +914,7 @@ void entropy_decode_mw_kernel(const uint8_t* __restrict__ in,
         const uint64_t out_before = i + (uint64_t)((scan & 0xFFFFu) - tlen_v);
         const bool invalid = lane < m &&
             (out_before >= bytes ||
-             (is_match && ((uint64_t)(word_v & 0x7FFFu) > out_before || (uint64_t)tlen_v > bytes - out_before)));
+             (is_match && ((uint64_t)(word_v & 0x7FFFu) > out_before + (kHist ? history : 0u) || (uint64_t)tlen_v > bytes - out_before)));
         const uint64_t inv = __ballot(invalid);
         if (inv != 0) { const int f = __builtin_ctzll(inv); if (f < m) { m = f; stop = true; } }
         int a_v = -1, b_v = -1;
@@ -1050,14 +1056,22 @@ __device__ __forceinline__ uint8_t load_l2(const uint8_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool kSkip>
+// kDict: the instantiation for blocks coded under a shared dictionary (SQZF version 3).  Every block's output is
+// preceded, virtually, by the D dictionary bytes: a source byte at offset s < 0 from the block's start is
+// dict[D + s].  The entropy stage has checked dist <= position + D.  Source offsets are signed here: o - dist
+// is negative for a source that starts in the dictionary, and an unsigned own-lane test would wrap.  The
+// whole-wave copy keeps its k % d form: its source bytes all lie in [at - d, at), in front of the copy, whether
+// that stretch is dictionary, output, or -- a periodic copy that starts in the dictionary -- some of each.
+// Without kDict the kernel is the one that never had the arguments.
+template <bool kSkip, bool kDict>
 __global__ __launch_bounds__(kWave, 4)          // four waves per SIMD: 16 streams per CU (the LDS allows as many)
 void lz_expand_kernel(const uint32_t* __restrict__ tokens,
                          const uint32_t* __restrict__ tok_count,
                          uint8_t* __restrict__ out,
                          const uint64_t* __restrict__ out_off,
                          uint32_t n_blocks,
-                         const uint32_t* __restrict__ skip) {       // optional, as in entropy_decode_kernel
+                         const uint32_t* __restrict__ skip,         // optional, as in entropy_decode_kernel
+                         const uint8_t* __restrict__ dict, uint32_t D) {
     const int lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
     if (b >= n_blocks) { return; }
@@ -1067,6 +1081,13 @@ void lz_expand_kernel(const uint32_t* __restrict__ tokens,
     uint8_t* dst = out + out_off[b];
     const uint32_t* tok = tokens + out_off[b];
     const uint32_t count = tok_count[b];      // tokens decoded before an error are still expanded
+    // kDict: the byte at signed offset s from the block's start (the clamp never acts on a checked stream: it keeps
+    // a read inside the dictionary whatever the tokens hold)
+    auto byte_at = [&](int64_t s) -> uint8_t {
+        if (s >= 0) { return load_l2(dst + s); }
+        const int64_t q = (int64_t)D + s;
+        return dict[q > 0 ? q : 0];
+    };
 
     uint64_t i = 0;                            // next output byte
     uint32_t next_word = (uint32_t)lane < count ? tok[lane] : 0u;
@@ -1086,8 +1107,24 @@ void lz_expand_kernel(const uint32_t* __restrict__ tokens,
         __threadfence_block();
         if (mine_in && !is_match) { dst[o] = (uint8_t)word; }
         // source entirely in front of this step, and short: my own lane copies it
-        const bool own = is_match && (o - dist) + mylen <= i && mylen <= (uint32_t)kExpOwnLane;
-        {   // four bytes per trip: the loads of a trip are independent of each other
+        bool own;
+        if constexpr (kDict) {
+            own = is_match && (int64_t)o - (int64_t)dist + (int64_t)mylen <= (int64_t)i && mylen <= (uint32_t)kExpOwnLane;
+        } else {
+            own = is_match && (o - dist) + mylen <= i && mylen <= (uint32_t)kExpOwnLane;
+        }
+        if constexpr (kDict) {
+            const int64_t sp = own ? (int64_t)o - (int64_t)dist : 0;
+            uint8_t* dp = dst + (own ? o : 0);
+            const uint32_t n_own = own ? mylen : 0u;
+            for (uint32_t k0 = 0; __ballot(k0 < n_own) != 0; k0 += 4) {
+                uint8_t v[4];
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++) { v[j] = k0 + j < n_own ? byte_at(sp + k0 + j) : (uint8_t)0; }
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++) { if (k0 + j < n_own) { dp[k0 + j] = v[j]; } }
+            }
+        } else {   // four bytes per trip: the loads of a trip are independent of each other
             const uint8_t* sp = dst + (own ? o - dist : 0);
             uint8_t* dp = dst + (own ? o : 0);
             const uint32_t n_own = own ? mylen : 0u;
@@ -1109,6 +1146,15 @@ void lz_expand_kernel(const uint32_t* __restrict__ tokens,
                                 (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)o, ml);
             const int len = (int)((w >> 16) & 0x1FFu);
             const int d = (int)(w & 0x7FFFu);
+            if constexpr (kDict) {
+                const int64_t from = (int64_t)at - (int64_t)d;             // < 0: the source starts in the dictionary
+                if (d >= len) {
+                    for (int k = lane; k < len; k += kWave) { dst[at + (uint64_t)k] = byte_at(from + k); }
+                } else {
+                    for (int k = lane; k < len; k += kWave) { dst[at + (uint64_t)k] = byte_at(from + (k % d)); }
+                }
+                continue;
+            }
             const uint8_t* sp = dst + (at - (uint64_t)d);
             // out[at+k] = out[at-d+(k mod d)]: only bytes in front of `at` are read
             if (d >= len) {
@@ -1122,24 +1168,24 @@ void lz_expand_kernel(const uint32_t* __restrict__ tokens,
 }
 
 namespace {
-template <bool kSkip>
+template <bool kSkip, bool kHist>
 void launch_entropy_decode_as(const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off,
                               uint32_t* tokens, uint32_t* tok_count, int32_t* err, uint64_t* end_bit,
                               uint32_t n_blocks, uint64_t start_bit, int waves, hipStream_t stream,
-                              const uint32_t* skip) {
+                              const uint32_t* skip, uint32_t history) {
     // waves per stream: 1 when the batch fills the chip by itself (16 streams per CU), 2 / 4 when it does not
     if (waves >= 8) {
-        hipLaunchKernelGGL((entropy_decode_mw_kernel<8, kSkip>), dim3(n_blocks), dim3(kWave * 8), 0, stream,
-                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip);
+        hipLaunchKernelGGL((entropy_decode_mw_kernel<8, kSkip, kHist>), dim3(n_blocks), dim3(kWave * 8), 0, stream,
+                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip, history);
     } else if (waves >= 4) {
-        hipLaunchKernelGGL((entropy_decode_mw_kernel<4, kSkip>), dim3(n_blocks), dim3(kWave * 4), 0, stream,
-                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip);
+        hipLaunchKernelGGL((entropy_decode_mw_kernel<4, kSkip, kHist>), dim3(n_blocks), dim3(kWave * 4), 0, stream,
+                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip, history);
     } else if (waves >= 2) {
-        hipLaunchKernelGGL((entropy_decode_mw_kernel<2, kSkip>), dim3(n_blocks), dim3(kWave * 2), 0, stream,
-                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip);
+        hipLaunchKernelGGL((entropy_decode_mw_kernel<2, kSkip, kHist>), dim3(n_blocks), dim3(kWave * 2), 0, stream,
+                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip, history);
     } else {
-        hipLaunchKernelGGL(entropy_decode_kernel<kSkip>, dim3(n_blocks), dim3(kWave), 0, stream,
-                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip);
+        hipLaunchKernelGGL((entropy_decode_kernel<kSkip, kHist>), dim3(n_blocks), dim3(kWave), 0, stream,
+                           in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, skip, history);
     }
 }
 } // namespace
@@ -1147,26 +1193,44 @@ void launch_entropy_decode_as(const uint8_t* in, const uint64_t* in_off, const u
 void launch_entropy_decode(const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off,
                            uint32_t* tokens, uint32_t* tok_count, int32_t* err, uint64_t* end_bit,
                            uint32_t n_blocks, uint64_t start_bit, int waves, hipStream_t stream,
-                           const uint32_t* skip) {
+                           const uint32_t* skip, uint32_t history) {
     if (n_blocks == 0) { return; }
-    if (skip != nullptr) {
-        launch_entropy_decode_as<true>(in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, waves,
-                                       stream, skip);
+    if (history != 0) {
+        if (skip != nullptr) {
+            launch_entropy_decode_as<true, true>(in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit,
+                                                 waves, stream, skip, history);
+        } else {
+            launch_entropy_decode_as<false, true>(in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit,
+                                                  waves, stream, skip, history);
+        }
+    } else if (skip != nullptr) {
+        launch_entropy_decode_as<true, false>(in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit,
+                                              waves, stream, skip, 0u);
     } else {
-        launch_entropy_decode_as<false>(in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit, waves,
-                                        stream, skip);
+        launch_entropy_decode_as<false, false>(in, in_off, out_off, tokens, tok_count, err, end_bit, n_blocks, start_bit,
+                                               waves, stream, skip, 0u);
     }
 }
 
 void launch_lz_expand(const uint32_t* tokens, const uint32_t* tok_count, uint8_t* out,
-                      const uint64_t* out_off, uint32_t n_blocks, hipStream_t stream, const uint32_t* skip) {
+                      const uint64_t* out_off, uint32_t n_blocks, hipStream_t stream, const uint32_t* skip,
+                      const uint8_t* dict, uint32_t dict_bytes) {
     if (n_blocks == 0) { return; }
-    if (skip != nullptr) {
-        hipLaunchKernelGGL(lz_expand_kernel<true>, dim3(n_blocks), dim3(kWave), 0, stream,
-                           tokens, tok_count, out, out_off, n_blocks, skip);
+    const uint8_t* const no_dict = nullptr;
+    if (dict != nullptr && dict_bytes != 0) {
+        if (skip != nullptr) {
+            hipLaunchKernelGGL((lz_expand_kernel<true, true>), dim3(n_blocks), dim3(kWave), 0, stream,
+                               tokens, tok_count, out, out_off, n_blocks, skip, dict, dict_bytes);
+        } else {
+            hipLaunchKernelGGL((lz_expand_kernel<false, true>), dim3(n_blocks), dim3(kWave), 0, stream,
+                               tokens, tok_count, out, out_off, n_blocks, skip, dict, dict_bytes);
+        }
+    } else if (skip != nullptr) {
+        hipLaunchKernelGGL((lz_expand_kernel<true, false>), dim3(n_blocks), dim3(kWave), 0, stream,
+                           tokens, tok_count, out, out_off, n_blocks, skip, no_dict, 0u);
     } else {
-        hipLaunchKernelGGL(lz_expand_kernel<false>, dim3(n_blocks), dim3(kWave), 0, stream,
-                           tokens, tok_count, out, out_off, n_blocks, skip);
+        hipLaunchKernelGGL((lz_expand_kernel<false, false>), dim3(n_blocks), dim3(kWave), 0, stream,
+                           tokens, tok_count, out, out_off, n_blocks, skip, no_dict, 0u);
     }
 }
 

@@ -949,6 +949,147 @@ void index_parse_kernel(const uint8_t* __restrict__ in,
 #endif
 }
 
+// ---------------------------------------------------------------------------
+// Shared dictionary (SQZF version 3): the longest match whose source STARTS in the dictionary, merged into the
+// match table index_match_kernel left.  A block under a dictionary Dct is coded as the bytes Dct || B from
+// position D = len(Dct) on, so a dictionary position q is the candidate at distance D - q + i of block position
+// i: every in-block candidate is nearer than every dictionary candidate, and the dictionary's match replaces the
+// table's only when it is STRICTLY longer (nearest among equals).  Dictionary candidates nearest first:
+// q = D-1 and q = D-2, whose 3-byte prefix runs on into the block and therefore has no entry in the index, then
+// the run of the index with the position's own prefix from its highest position down.  A source that starts in
+// the dictionary runs on into the block (Dct[D-1] is followed by B[0]), and may run on over position i itself.
+//
+// One workgroup holds the dictionary (at most 32,767 bytes) and its sorted positions (16 bits each, at most
+// 64 KB) in LDS, loaded once with 16-byte loads, and then works through blocks blockIdx.x, + gridDim.x, ...:
+// one thread per position.  A position finds both ends of its prefix's run by two bisections over the sorted
+// positions (15 steps of two LDS reads each); every candidate compare reads the dictionary from LDS, four bytes at a time;
+// only the position's own bytes (consecutive threads, consecutive bytes) and a source's tail inside the block
+// come from memory.  Positions i >= window - 1 cannot reach the dictionary and are not visited.
+#ifndef SQZ_DICT_THREADS
+#define SQZ_DICT_THREADS 1024                     // (the CPU wave emulator of tests/emu runs workgroups of up to 8 waves)
+#endif
+constexpr int kDictThreads = SQZ_DICT_THREADS;
+struct DictLds {
+    uint8_t byte[kMaxWindow];                    // the dictionary, zeros behind its end
+    uint16_t rank[kMaxWindow];                   // positions 0 .. D-3 by 3-byte prefix, ascending inside a run
+};                                               // 96 KB: one workgroup (16 waves) per CU
+
+__global__ __launch_bounds__(kDictThreads)
+void dict_match_kernel(const uint8_t* __restrict__ in,
+                       const uint64_t* __restrict__ in_off,
+                       uint32_t n_blocks, uint32_t window,
+                       const uint8_t* __restrict__ dict, uint32_t D,
+                       const uint32_t* __restrict__ dsorted,      // index_sort_kernel's result for the dictionary
+                       uint32_t* __restrict__ match, uint64_t slots) {
+    __shared__ __attribute__((aligned(16))) DictLds lds;
+    const uint32_t tid = threadIdx.x;
+    if (D == 0 || D >= (uint32_t)kMaxWindow) { return; }          // (the callers refuse these)
+    const uint32_t cnt = D >= 3 ? D - 2 : 0u;                     // positions with an entry in the index
+    {
+        // the dictionary: whole 16-byte groups where its address allows them, bytes otherwise; zeros to the end
+        const bool aligned = (reinterpret_cast<uintptr_t>(dict) & 15u) == 0;
+        const uint32_t groups = aligned ? D / 16u : 0u;
+        for (uint32_t g = tid; g < groups; g += (uint32_t)kDictThreads) {
+            reinterpret_cast<uint4*>(lds.byte)[g] = reinterpret_cast<const uint4*>(dict)[g];
+        }
+        for (uint32_t k = groups * 16u + tid; k < (uint32_t)kMaxWindow; k += (uint32_t)kDictThreads) {
+            lds.byte[k] = k < D ? dict[k] : (uint8_t)0;
+        }
+        // the sorted positions: four 32-bit words in, four 16-bit values out (the array is the sort's: 256-byte
+        // aligned, D + 64 slots; what lies behind cnt is never looked at)
+        const uint32_t quads = (cnt + 3u) / 4u;
+        for (uint32_t g = tid; g < quads; g += (uint32_t)kDictThreads) {
+            const uint4 v = reinterpret_cast<const uint4*>(dsorted)[g];
+            SortCntPair* const two = reinterpret_cast<SortCntPair*>(lds.rank) + 2u * g;   // two 16-bit values per word
+            two[0] = (v.x & 0xFFFFu) | (v.y << 16);
+            two[1] = (v.z & 0xFFFFu) | (v.w << 16);
+        }
+    }
+    __syncthreads();
+    auto lds_u32 = [&](uint32_t at) { return reinterpret_cast<const U32u*>(lds.byte + at)->v; };   // at + 4 <= 32768
+    auto dkey = [&](uint32_t p) { return __builtin_bswap32(lds_u32(p)) >> 8; };                     // p <= D - 3
+    const uint32_t reach = window - 1u;
+
+    for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        if (in_off[b + 1] > slots) { continue; }                  // beyond the caller's arrays: index_parse refuses the block
+        const uint8_t* src = in + in_off[b];
+        const uint64_t bytes = in_off[b + 1] - in_off[b];
+        if (bytes < 3) { continue; }
+        uint32_t* M = match + in_off[b];
+        // positions with a table word (the last two have none) that can reach Dct[D-1]: i + 1 <= window - 1
+        const uint64_t upto = bytes - 2 < (uint64_t)reach ? bytes - 2 : (uint64_t)reach;
+        for (uint32_t i = tid; i < (uint32_t)upto; i += (uint32_t)kDictThreads) {
+            const uint64_t left = bytes - i;
+            const uint32_t cap = left < (uint64_t)kLenMax ? (uint32_t)left : (uint32_t)kLenMax;
+            uint32_t best = M[i] >> 16;                           // the in-block match to beat (0: a literal)
+            if (best >= cap) { continue; }
+            const uint32_t q_min = D + i > reach ? D + i - reach : 0u;   // the farthest dictionary position within reach
+            // byte v of Dct || B
+            auto vbyte = [&](uint32_t v) { return v < D ? lds.byte[v] : src[v - D]; };
+            // how far Dct || B at q agrees with B at i, up to cap
+            auto extend = [&](uint32_t q) {
+                const uint32_t in_d = D - q < cap ? D - q : cap;  // the part of the source inside the dictionary
+                uint32_t k = 0;
+                while (k < in_d) {
+                    if (k + 4 <= in_d) {                          // (k + 4 <= cap <= bytes - i: the own dword exists)
+                        const uint32_t x = lds_u32(q + k) ^ load_u32_unaligned(src + i + k);
+                        if (x != 0) { return k + ((uint32_t)__builtin_ctz(x) >> 3); }
+                        k += 4;
+                    } else {
+                        if (lds.byte[q + k] != src[i + k]) { return k; }
+                        k++;
+                    }
+                }
+                while (k < cap) {                                 // on into the block: source byte q + k - D < k
+                    const uint32_t s = q + k - D;
+                    if (k + 4 <= cap) {
+                        const uint32_t x = load_u32_unaligned(src + s) ^ load_u32_unaligned(src + i + k);
+                        if (x != 0) { return k + ((uint32_t)__builtin_ctz(x) >> 3); }
+                        k += 4;
+                    } else {
+                        if (src[s] != src[i + k]) { return k; }
+                        k++;
+                    }
+                }
+                return k;
+            };
+            uint32_t dist = 0;
+            uint8_t own_next = best >= (uint32_t)kLenMin ? src[i + best] : (uint8_t)0;     // best < cap: i + best < bytes
+            auto consider = [&](uint32_t q) {
+                if (best >= (uint32_t)kLenMin && vbyte(q + best) != own_next) { return; }  // cannot be longer
+                const uint32_t len = extend(q);
+                if (len >= (uint32_t)kLenMin && len > best) {     // strictly longer: nearest among equals
+                    best = len; dist = D + i - q;
+                    if (best < cap) { own_next = src[i + best]; }
+                }
+            };
+            if (D - 1u >= q_min) { consider(D - 1u); }
+            if (D >= 2u && D - 2u >= q_min && best < cap) { consider(D - 2u); }
+            if (cnt != 0 && best < cap) {
+                const uint32_t key = sort_key(src, bytes, i);     // i <= bytes - 3
+                uint32_t lo = 0, hi = cnt;                        // `end`: the first rank whose key is greater than mine
+                while (lo < hi) {
+                    const uint32_t mid = lo + ((hi - lo) >> 1);
+                    if (dkey(lds.rank[mid]) <= key) { lo = mid + 1; } else { hi = mid; }
+                }
+                uint32_t end = lo;
+                lo = 0; hi = end;                                 // `begin`: the first rank whose key is mine (end: none)
+                while (lo < hi) {
+                    const uint32_t mid = lo + ((hi - lo) >> 1);
+                    if (dkey(lds.rank[mid]) < key) { lo = mid + 1; } else { hi = mid; }
+                }
+                const uint32_t begin = lo;
+                while (end > begin && best < cap) {               // the run, nearest first: no prefix to look at again
+                    const uint32_t q = lds.rank[--end];
+                    if (q < q_min) { break; }                     // everything further is farther
+                    consider(q);
+                }
+            }
+            if (dist != 0) { M[i] = (best << 16) | dist; }
+        }
+    }
+}
+
 void launch_index_sort(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
                        uint32_t* buf_a, uint32_t* buf_b, uint64_t slots,
                        hipStream_t stream) {
@@ -982,6 +1123,15 @@ void launch_index_parse_lazy(const uint8_t* in, const uint64_t* in_off, uint32_t
     if (n_blocks == 0) { return; }
     hipLaunchKernelGGL(index_parse_kernel<true>, dim3(n_blocks), dim3(kWave), 0, stream,
                        in, in_off, n_blocks, match, tokens, tok_count, slots);
+}
+
+void launch_dict_match(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks, uint32_t window,
+                       const uint8_t* dict, uint32_t dict_bytes, const uint32_t* dict_sorted,
+                       uint32_t* match, uint64_t slots, hipStream_t stream) {
+    if (n_blocks == 0) { return; }
+    const uint32_t grid = n_blocks < 1024u ? n_blocks : 1024u;  // a workgroup loads the dictionary once and takes every grid-th block
+    hipLaunchKernelGGL(dict_match_kernel, dim3(grid), dim3(kDictThreads), 0, stream,
+                       in, in_off, n_blocks, window, dict, dict_bytes, dict_sorted, match, slots);
 }
 
 } // namespace sqzk

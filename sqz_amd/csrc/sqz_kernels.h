@@ -32,6 +32,12 @@ void launch_index_match(const uint8_t* in, const uint64_t* in_off, uint32_t n_bl
 void launch_index_parse(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
                         const uint32_t* match, uint32_t* tokens, uint32_t* tok_count,
                         uint64_t slots, hipStream_t stream);
+// shared dictionary (SQZF version 3), between launch_index_match and either parse: the longest match whose source
+// starts in dict[0 .. dict_bytes), 1 <= dict_bytes <= 32767, merged into `match` where it is strictly longer.
+// dict_sorted: launch_index_sort's result for the dictionary as a one-block batch.
+void launch_dict_match(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks, uint32_t window,
+                       const uint8_t* dict, uint32_t dict_bytes, const uint32_t* dict_sorted,
+                       uint32_t* match, uint64_t slots, hipStream_t stream);
 // the one-step lazy parse over the same match table (not the reference's token sequence; any decoder reads it)
 void launch_index_parse_lazy(const uint8_t* in, const uint64_t* in_off, uint32_t n_blocks,
                              const uint32_t* match, uint32_t* tokens, uint32_t* tok_count,
@@ -56,10 +62,12 @@ void launch_tree_debug(const int32_t* symbols, uint32_t count, int which, int ba
 void launch_entropy_decode(const uint8_t* in, const uint64_t* in_off, const uint64_t* out_off,
                            uint32_t* tokens, uint32_t* tok_count, int32_t* err, uint64_t* end_bit,
                            uint32_t n_blocks, uint64_t start_bit, int waves, hipStream_t stream,
-                           const uint32_t* skip = nullptr);
+                           const uint32_t* skip = nullptr, uint32_t history = 0);
+// history / dict: every block is preceded by the same `history` = dict_bytes dictionary bytes, which distances may
+// reach into (the entropy stage refuses dist > position + history; 0 is a batch without a dictionary)
 void launch_lz_expand(const uint32_t* tokens, const uint32_t* tok_count, uint8_t* out,
                       const uint64_t* out_off, uint32_t n_blocks, hipStream_t stream,
-                      const uint32_t* skip = nullptr);
+                      const uint32_t* skip = nullptr, const uint8_t* dict = nullptr, uint32_t dict_bytes = 0);
 
 // the reference's HEAD range coder (range_coder.hip): literal-only encode as HEAD
 // runs it, decode as written.  Block b: in[in_off[b] .. in_off[b+1]) -> out + out_off[b], at most

@@ -3,41 +3,69 @@
 Host flavour (bytes in, bytes out) and a device flavour over torch tensors in the style of batch.py.
 Every byte of codec and checksum work happens in libsqz_amd.so; nothing is computed here.
 
-    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18] [--store] [--lazy]    compress a file
-    python -m sqz_amd.frame d IN OUT                                       decompress one
+    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18] [--store] [--lazy] [--dict FILE]   compress a file
+    python -m sqz_amd.frame d IN OUT [--dict FILE]                         decompress one
     python -m sqz_amd.frame info IN                                        describe one
     python -m sqz_amd.frame blocks IN                                      one line per block
 
 store=True / --store writes version 2: a block whose stream is not smaller than its content is stored as it is.
 parse="lazy" / --lazy encodes with one position of look-ahead (codec.parse_code): smaller streams in the same frame
 format, read by every reader; the default, "greedy", is the reference's parse.
+dictionary=bytes / --dict FILE writes version 3: every block may reach back into the dictionary (1 .. window - 1
+bytes) as if it stood in front of the block.  The frame records the dictionary's length and CRC-32, not the
+dictionary: the reader brings the same bytes (anything else is EILSEQ).  For frames of small blocks of text; it can
+make an executable larger (README).
 """
 import ctypes as C
 import errno
 
 from . import _native as N
-from .codec import PARSE_LAZY, SqzError, _raise, parse_code
+from .codec import PARSE_LAZY, SqzError, _raise, dict_bytes, parse_code
 
 HEADER_BYTES = 32
 FRAME_STORED = 1            # SQZ_FRAME_STORED
+FRAME_DICT = 2              # SQZ_FRAME_DICT
 
 
 def _flags(store: bool) -> int:
     return FRAME_STORED if store else 0
 
 
-def frame_bound(nbytes: int, block_bits: int = 18, store: bool = False) -> int:
+def frame_bound(nbytes: int, block_bits: int = 18, store: bool = False, dictionary: bool = False) -> int:
     """worst-case size of the frame of `nbytes` bytes of content"""
+    if dictionary:
+        return int(N.lib().sqz_frame_bound_dict(nbytes, block_bits, _flags(store) | FRAME_DICT))
     return int(N.lib().sqz_frame_bound_ex(nbytes, block_bits, _flags(store)))
+
+
+class _FrameInfo(dict):
+    """frame_info()'s result.  A version-3 header has a dictionary record, and its two fields are keys; versions 1
+    and 2 have none: there the fields read as 0 without being keys, so the dict still equals the header's own
+    fields."""
+
+    def __missing__(self, key):
+        if key in ("dict_bytes", "dict_crc"):
+            return 0
+        raise KeyError(key)
 
 
 def frame_info(frame) -> dict:
     """The header's fields (sqz_frame_info), checked; with the index in reach, that too.
+    dict_bytes / dict_crc: the record of a version-3 frame (0 while it is not in reach).  For versions 1 and 2, which
+    have no record, info["dict_bytes"] and info["dict_crc"] READ as 0 but are NOT keys of the result: `in`, .get(),
+    iteration and the `info` tool show them for a version-3 frame only, so that the result of an older frame keeps
+    exactly the header's own eight fields.  Test the version (info["version"] == 3), not the key.
     Host code: no device is touched."""
     frame = bytes(frame)
     fi = N.FrameInfo()
     _raise(N.lib().sqz_frame_info(frame, len(frame), C.byref(fi)), "sqz_frame_info")
-    return {k: int(getattr(fi, k)) for k, _ in N.FrameInfo._fields_ if k != "reserved"}
+    info = _FrameInfo({k: int(getattr(fi, k)) for k, _ in N.FrameInfo._fields_ if k != "reserved"})
+    if fi.version == 3:
+        nb, crc = C.c_uint32(0), C.c_uint32(0)
+        if len(frame) >= fi.payload_off:
+            _raise(N.lib().sqz_frame_dict(frame, len(frame), C.byref(nb), C.byref(crc)), "sqz_frame_dict")
+        info["dict_bytes"], info["dict_crc"] = nb.value, crc.value
+    return info
 
 
 def frame_blocks(frame) -> list:
@@ -51,16 +79,20 @@ def frame_blocks(frame) -> list:
 
 
 def compress_frame(data, win_bits: int = 15, block_bits: int = 18, store: bool = False,
-                   parse: str = "greedy") -> bytes:
+                   parse: str = "greedy", dictionary=None) -> bytes:
     lazy = parse_code(parse) == PARSE_LAZY
+    dct = dict_bytes(dictionary, 1 << win_bits) if dictionary is not None else None
     data = bytes(data)
-    cap = frame_bound(len(data), block_bits, store)
+    cap = frame_bound(len(data), block_bits, store, dct is not None)
     if cap == 0:
         raise SqzError(errno.EINVAL, "sqz_frame_compress: block_bits out of range")
     out = bytearray(cap)
     n = C.c_uint64(0)
     dst = (C.c_uint8 * cap).from_buffer(out)
-    if lazy:
+    if dct is not None:
+        _raise(N.lib().sqz_frame_compress_dict(data, len(data), win_bits, block_bits, _flags(store), parse_code(parse),
+                                               dct, len(dct), dst, cap, C.byref(n)), "sqz_frame_compress_dict")
+    elif lazy:
         _raise(N.lib().sqz_frame_compress_parse(data, len(data), win_bits, block_bits, _flags(store), PARSE_LAZY, dst,
                                                 cap, C.byref(n)), "sqz_frame_compress_parse")
     else:
@@ -70,17 +102,23 @@ def compress_frame(data, win_bits: int = 15, block_bits: int = 18, store: bool =
     return bytes(out[:n.value])
 
 
-def decompress_frame(frame, return_errors: bool = False):
+def decompress_frame(frame, return_errors: bool = False, dictionary=None):
     """The content of a frame.  A block that fails raises SqzError with the first errno; its attribute
     block_errors lists every block's.  return_errors=True returns (bytes, block_errors) instead: good
-    blocks are delivered, bad ones hold whatever the decoder produced."""
+    blocks are delivered, bad ones hold whatever the decoder produced.  dictionary: what a version-3 frame was
+    written with (a wrong one is EILSEQ; a version-3 frame without one, or another frame with one, EINVAL)."""
+    dct = dict_bytes(dictionary) if dictionary is not None else None
     frame = bytes(frame)
     fi = frame_info(frame[:HEADER_BYTES])
     out = bytearray(max(fi["content_bytes"], 1))
     dst = (C.c_uint8 * len(out)).from_buffer(out)
     errs = (C.c_int32 * max(fi["n_blocks"], 1))()
     n = C.c_uint64(0)
-    rc = N.lib().sqz_frame_decompress(frame, len(frame), dst, fi["content_bytes"], C.byref(n), errs)
+    if dct is not None:
+        rc = N.lib().sqz_frame_decompress_dict(frame, len(frame), dct, len(dct), dst, fi["content_bytes"], C.byref(n),
+                                               errs)
+    else:
+        rc = N.lib().sqz_frame_decompress(frame, len(frame), dst, fi["content_bytes"], C.byref(n), errs)
     del dst
     block_errors = list(errs)[:fi["n_blocks"]]
     if return_errors and (rc == 0 or any(block_errors)):
@@ -92,15 +130,20 @@ def decompress_frame(frame, return_errors: bool = False):
     return bytes(out[:n.value])
 
 
-def read_range(frame, offset: int, length: int) -> bytes:
-    """content[offset : offset + length]: only the covering blocks are uploaded, decoded and verified"""
+def read_range(frame, offset: int, length: int, dictionary=None) -> bytes:
+    """content[offset : offset + length]: only the covering blocks are uploaded, decoded and verified.
+    dictionary: as for decompress_frame."""
+    dct = dict_bytes(dictionary) if dictionary is not None else None
     frame = bytes(frame)
     content = frame_info(frame[:HEADER_BYTES])["content_bytes"]
     out = bytearray(max(min(length, content), 1))            # a range that leaves the content is refused below
     dst = (C.c_uint8 * len(out)).from_buffer(out)
-    rc = N.lib().sqz_frame_read(frame, len(frame), offset, length, dst)
+    if dct is not None:
+        rc = N.lib().sqz_frame_read_dict(frame, len(frame), dct, len(dct), offset, length, dst)
+    else:
+        rc = N.lib().sqz_frame_read(frame, len(frame), offset, length, dst)
     del dst
-    _raise(rc, "sqz_frame_read")
+    _raise(rc, "sqz_frame_read_dict" if dct is not None else "sqz_frame_read")
     return bytes(out[:length])
 
 
@@ -209,9 +252,12 @@ def main(argv=None) -> int:
     c.add_argument("--block-bits", type=int, default=18)
     c.add_argument("--store", action="store_true", help="version 2: store a block whose stream is not smaller")
     c.add_argument("--lazy", action="store_true", help="lazy parse: smaller streams, same format (not the reference's bytes)")
+    c.add_argument("--dict", dest="dictionary", metavar="FILE",
+                   help="version 3: every block may reach back into FILE's bytes (1 .. window - 1 of them)")
     d = sub.add_parser("d", help="decompress IN to OUT")
     d.add_argument("src")
     d.add_argument("dst")
+    d.add_argument("--dict", dest="dictionary", metavar="FILE", help="the dictionary a version-3 frame was written with")
     i = sub.add_parser("info", help="describe IN")
     i.add_argument("src")
     k = sub.add_parser("blocks", help="one line per block of IN")
@@ -219,11 +265,19 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     with open(a.src, "rb") as fh:
         blob = fh.read()
+    dct = None
+    if getattr(a, "dictionary", None):
+        with open(a.dictionary, "rb") as fh:
+            dct = fh.read()
     try:
         if a.cmd == "c":
-            out = compress_frame(blob, a.win_bits, a.block_bits, a.store, "lazy" if a.lazy else "greedy")
+            parse = "lazy" if a.lazy else "greedy"
+            if dct is None:
+                out = compress_frame(blob, a.win_bits, a.block_bits, a.store, parse)
+            else:
+                out = compress_frame(blob, a.win_bits, a.block_bits, a.store, parse, dictionary=dct)
         elif a.cmd == "d":
-            out = decompress_frame(blob)
+            out = decompress_frame(blob) if dct is None else decompress_frame(blob, dictionary=dct)
         elif a.cmd == "blocks":
             for b, blk in enumerate(frame_blocks(blob)):
                 print(f"{b}: " + " ".join(f"{key}={v}" for key, v in blk.items()))
@@ -232,7 +286,7 @@ def main(argv=None) -> int:
             for k, v in frame_info(blob).items():
                 print(f"{k}: {v}")
             return 0
-    except SqzError as e:
+    except (SqzError, ValueError) as e:
         print(f"sqz_amd.frame: {e}", flush=True)
         return 1
     with open(a.dst, "wb") as fh:
