@@ -24,7 +24,10 @@
 //                       min(i, window-1), keep the first strictly longer match,
 //                       stop at len == min(bytes-i, 257).  -> match[i].  A wave whose
 //                       64 ranks lie inside one run walks the candidates once for
-//                       all its lanes; a stream's workgroups share one XCD.
+//                       all its lanes; a stream's workgroups share one XCD.  A wave's
+//                       pages cost a fixed two loads and one store each, the loads issued
+//                       one and two pages ahead, and nothing waits for the scattered store
+//                       of the page before.
 //   index_parse_kernel  one wavefront per stream: the greedy step
 //                       (squeeze.h:377-394) over match[] -> the token words of
 //                       stage 1 (same format as lz77_scan.hip), found by per-chunk
@@ -372,6 +375,52 @@ void index_sort_kernel(const uint8_t* __restrict__ in,
 }
 
 // ---------------------------------------------------------------------------
+// index_match_kernel.  A wave works through its pages (64 consecutive ranks each) with a FIXED number of memory
+// operations per page, none of them behind a divergent branch, and with the next pages' loads in flight:
+//   * every lane loads S from a clamped rank (the last valid rank again where the page runs over the end), two
+//     pages ahead;
+//   * every lane loads its position's 16 bytes with one unaligned 16-byte load from min(i, n - 16), one page ahead
+//     (as soon as that page's S is there); a position in the stream's last 15 bytes shifts what it got right by
+//     i - (n - 16) bytes, zero-filled -- the bytes the stream has from i on, zeros behind its end;
+//   * every lane stores its match word; a lane without a rank stores the page's last valid word to that word's
+//     position again (as the sort's copy-out does).
+// Both loads sit in a register double buffer.  gfx950 counts stores in vmcnt like loads, so a wait for "everything"
+// at the top of a page is also a wait for the scattered store of the page before to be acknowledged -- and that
+// store is the slowest operation of the kernel.  With the loads issued ahead, what a page's compare needs set out
+// BEFORE the store of the page before it: the top of a page waits for nothing, and the one wait of the loop stands
+// at the end of a page's compute, in front of the page's own store (as compiled: the `s_waitcnt vmcnt` figures are
+// in DESIGN.md section 5).  The first page stands apart from the loop, so that the loop is entered with the same
+// operations in flight as its back edge has (the compiler's wait counts are the minimum over both ways in).  Blocks
+// shorter than 16 bytes (no 16-byte load fits) are one page of at most 13 positions: its lanes walk by themselves.
+struct __attribute__((packed)) U128u { uint32_t w[4]; };
+
+// Section timers of the instrumented build (tools/build_stats.sh): cycles of wave 0 of block 1 per section, summed
+// over its pages.  0 the page's positions and bytes have arrived (the instrumented build waits for them there:
+// vmcnt(0), which also waits for the store of the page before), 1 candidate loop (shared walk or several runs),
+// 2 own walks of the lanes the registers could not settle, 3 store issue.
+struct MatchSec {
+#ifdef SQZ_STATS
+    uint64_t t[4] = {0, 0, 0, 0};
+    uint64_t last = 0;
+#endif
+};
+#ifdef SQZ_STATS
+#define MATCH_SEC(s, k) SORT_SEC(s, k)
+#define MATCH_SEC_LOADS(s, k) SORT_SEC_LOADS(s, k)
+#else
+#define MATCH_SEC(s, k)
+#define MATCH_SEC_LOADS(s, k)
+#endif
+
+// bytes k.. of the 16 in w0..w3 move to the front, zeros follow (k = 0..15)
+__device__ __forceinline__ void drop_bytes(uint32_t& w0, uint32_t& w1, uint32_t& w2, uint32_t& w3, uint32_t k) {
+    uint64_t lo = ((uint64_t)w1 << 32) | w0, hi = ((uint64_t)w3 << 32) | w2;
+    const uint32_t s = 8u * k;
+    if (s >= 64u) { lo = hi >> (s - 64u); hi = 0; }
+    else if (s != 0u) { lo = (lo >> s) | (hi << (64u - s)); hi >>= s; }
+    w0 = (uint32_t)lo; w1 = (uint32_t)(lo >> 32); w2 = (uint32_t)hi; w3 = (uint32_t)(hi >> 32);
+}
+
 __global__ __launch_bounds__(256)
 void index_match_kernel(const uint8_t* __restrict__ in,
                         const uint64_t* __restrict__ in_off,
@@ -408,220 +457,274 @@ void index_match_kernel(const uint8_t* __restrict__ in,
     const uint32_t wave_id = group * (blockDim.x / (uint32_t)kWave) + (threadIdx.x - (uint32_t)lane) / (uint32_t)kWave;
     const uint32_t page_lo = wave_id * per_wave;
     const uint32_t page_hi = page_lo + per_wave < pages ? page_lo + per_wave : pages;
-    // a position's first 16 bytes (zeros beyond the stream's end: never compared, lengths stop at cap <= n - i)
-    auto load16 = [&](uint32_t at, uint32_t& w0, uint32_t& w1, uint32_t& w2, uint32_t& w3) {
-        if (at + 16 <= n) {
-            w0 = load_u32_unaligned(src + at); w1 = load_u32_unaligned(src + at + 4);
-            w2 = load_u32_unaligned(src + at + 8); w3 = load_u32_unaligned(src + at + 12);
-        } else {
-            uint32_t w[4] = {0, 0, 0, 0};
-            for (uint32_t k = 0; k < 16 && at + k < n; k++) { w[k >> 2] |= (uint32_t)src[at + k] << (8 * (k & 3)); }
-            w0 = w[0]; w1 = w[1]; w2 = w[2]; w3 = w[3];
+    if (page_lo >= page_hi) { return; }
+    MatchSec sec;
+#ifdef SQZ_STATS
+    sec.last = __builtin_readcyclecounter();
+    const uint64_t sec_begin = sec.last;
+#endif
+    // one lane on its own: the candidates of ranks q_from-1, q_from-2, ... (nearest first).
+    // Where the walk ends -- the first rank of the run, or the first candidate within reach, whichever is
+    // later -- is found FIRST (ranks are in position order inside a run, so "same key and within reach" is
+    // monotone: doubling steps, then bisection), and the lane's own byte at the length to beat is kept in
+    // a register: what is left per candidate is its position (neighbouring lanes read neighbouring ranks)
+    // and ONE scattered byte, where it used to be three scattered loads.  These walks are gather-bound
+    // (executables: a thousand candidates per position).  They are the rare path: their loads wait for everything.
+    auto walk = [&](const uint32_t q_from, const uint32_t i, const uint32_t key, const uint32_t cap, const uint32_t reach,
+                    uint32_t& best, uint32_t& dist) __attribute__((always_inline)) {
+        if (q_from == 0 || best >= cap) { return; }
+        auto inside = [&](uint32_t r) {                    // r < q_from <= own rank: S[r] < i when the key is the same
+            const uint32_t p = S[r];
+            if (p + 4 > n) { return false; }               // (another key's position may end the stream)
+            return (load_u32_unaligned(src + p) & 0x00FFFFFFu) == key && i - p <= reach;
+        };
+        uint32_t q_lo;                                     // candidates are ranks [q_lo, q_from)
+        {
+            uint32_t d = 4, bad = 0, good = q_from;       // ranks < bad... : `bad - 1` is outside or bad == 0
+            bool open = true;
+            while (open) {
+                if (d >= q_from) { bad = 0; open = false; if (inside(0)) { good = 0; } else { bad = 1; } }
+                else if (inside(q_from - d)) { good = q_from - d; d <<= 1; }
+                else { bad = q_from - d + 1; open = false; }
+            }
+            // first inside rank is in [bad, good]
+            uint32_t lo = bad, hi = good;
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (inside(mid)) { hi = mid; } else { lo = mid + 1; }
+            }
+            q_lo = lo;
+        }
+        uint8_t own_next = best >= (uint32_t)kLenMin ? src[i + best] : (uint8_t)0;   // best < cap: i + best < n
+        for (uint32_t q = q_from; q > q_lo && best < cap; ) {
+            q--;
+            const uint32_t p = S[q];
+            if (best >= (uint32_t)kLenMin && src[p + best] != own_next) { continue; }
+            uint32_t k = 3;
+            while (k < cap) {
+                if (i + k + 4 <= n) {
+                    const uint32_t x = load_u32_unaligned(src + p + k) ^ load_u32_unaligned(src + i + k);
+                    if (x != 0) { k += (uint32_t)__builtin_ctz(x) >> 3; break; }
+                    k += 4;
+                } else {
+                    if (src[p + k] != src[i + k]) { break; }
+                    k++;
+                }
+            }
+            if (k > cap) { k = cap; }
+            if (k > best) {                                // strictly longer: nearest among equals
+                best = k; dist = i - p;
+                if (best < cap) { own_next = src[i + best]; }
+            }
         }
     };
-    // the page in front of the current one: positions and their first 8 bytes (lane = rank inside the page)
-    uint32_t prev_i = 0, prev0 = 0, prev1 = 0, prev2 = 0, prev3 = 0;
-    if (page_lo > 0 && page_lo < page_hi) {                  // (every rank of an earlier page exists)
-        prev_i = S[(page_lo - 1u) * (uint32_t)kWave + (uint32_t)lane];
-        load16(prev_i, prev0, prev1, prev2, prev3);
+    if (n < 16u) {
+        // ---- a block shorter than 16 bytes: at most 13 positions, one page, and no room for a 16-byte load ----
+        // (block-uniform, outside the page pipeline)  Every lane walks its own run, which is the same search.
+        if ((uint32_t)lane < count) {
+            const uint32_t i = S[lane];
+            const uint32_t key = (uint32_t)src[i] | ((uint32_t)src[i + 1] << 8) | ((uint32_t)src[i + 2] << 16);   // i <= n - 3
+            const uint32_t cap = n - i;
+            const uint32_t reach = i < window - 1 ? i : window - 1;
+            uint32_t best = 0, dist = 0;
+            walk((uint32_t)lane, i, key, cap, reach, best, dist);
+            M[i] = best >= (uint32_t)kLenMin ? ((best << 16) | dist) : (key & 0xFFu);
+        }
+        return;
     }
-    for (uint32_t pg = page_lo; pg < page_hi; pg++) {
+    const uint32_t tail = n - 16u;                           // the last position a 16-byte load may start at
+    const uint32_t page_last = page_hi - 1u;
+    // the S value of this lane's rank in page pg: a page behind the wave's last one is the last one again, a rank
+    // behind the stream's last one is the last one again -- always a load, always inside S[0, count)
+    auto fetch_pos = [&](uint32_t pg) {
+        const uint32_t r = (pg < page_last ? pg : page_last) * (uint32_t)kWave + (uint32_t)lane;
+        return S[r < count - 1u ? r : count - 1u];
+    };
+    auto fetch16 = [&](uint32_t at) { return *reinterpret_cast<const U128u*>(src + (at < tail ? at : tail)); };
+    // what fetch16(at) brought, as the 16 bytes from `at` on (zeros beyond the stream's end: never compared, lengths
+    // stop at cap <= n - i).  Only the stream's last 15 positions have anything to do here.
+    auto settle16 = [&](uint32_t at, const U128u& got, uint32_t& w0, uint32_t& w1, uint32_t& w2, uint32_t& w3) {
+        w0 = got.w[0]; w1 = got.w[1]; w2 = got.w[2]; w3 = got.w[3];
+        if (__ballot(at > tail) != 0) { drop_bytes(w0, w1, w2, w3, at > tail ? at - tail : 0u); }
+    };
+    // the page in front of the current one: positions and their first 16 bytes (lane = rank inside the page)
+    uint32_t prev_i = 0, prev0 = 0, prev1 = 0, prev2 = 0, prev3 = 0;
+
+    // ---- one page: position i and its bytes are in registers ---------------------------------------------
+    auto do_page = [&](const uint32_t pg, const uint32_t i, const uint32_t own0, const uint32_t own1,
+                       const uint32_t own2, const uint32_t own3) __attribute__((always_inline)) {
+        MATCH_SEC_LOADS(sec, 0)
         const uint32_t r0 = pg * (uint32_t)kWave;
         const bool have_prev = pg > 0;
         const uint32_t r = r0 + (uint32_t)lane;              // a wave owns 64 consecutive ranks
-        const bool valid = r < count;
-        const uint32_t i = valid ? S[r] : 0u;
+        const bool valid = r < count;                        // (a lane without a rank holds the last rank's position)
         const uint32_t cap = (n - i) < (uint32_t)kLenMax ? (n - i) : (uint32_t)kLenMax;
         const uint32_t reach = i < window - 1 ? i : window - 1;
-        uint32_t own0 = 0, own1 = 0, own2 = 0, own3 = 0;
-        if (valid) { load16(i, own0, own1, own2, own3); }
         const uint32_t key = own0 & 0x00FFFFFFu;             // i <= n - 3: the key's bytes are the stream's
         uint32_t best = 0, dist = 0;
-        // one lane on its own: the candidates of ranks q_from-1, q_from-2, ... (nearest first).
-        // Where the walk ends -- the first rank of the run, or the first candidate within reach, whichever is
-        // later -- is found FIRST (ranks are in position order inside a run, so "same key and within reach" is
-        // monotone: doubling steps, then bisection), and the lane's own byte at the length to beat is kept in
-        // a register: what is left per candidate is its position (neighbouring lanes read neighbouring ranks)
-        // and ONE scattered byte, where it used to be three scattered loads.  These walks are gather-bound
-        // (executables: a thousand candidates per position).
-        auto walk = [&](uint32_t q_from) {
-            if (q_from == 0 || best >= cap) { return; }
-            auto inside = [&](uint32_t r) {                    // r < q_from <= own rank: S[r] < i when the key is the same
-                const uint32_t p = S[r];
-                if (p + 4 > n) { return false; }               // (another key's position may end the stream)
-                return (load_u32_unaligned(src + p) & 0x00FFFFFFu) == key && i - p <= reach;
-            };
-            uint32_t q_lo;                                     // candidates are ranks [q_lo, q_from)
-            {
-                uint32_t d = 4, bad = 0, good = q_from;       // ranks < bad... : `bad - 1` is outside or bad == 0
-                bool open = true;
-                while (open) {
-                    if (d >= q_from) { bad = 0; open = false; if (inside(0)) { good = 0; } else { bad = 1; } }
-                    else if (inside(q_from - d)) { good = q_from - d; d <<= 1; }
-                    else { bad = q_from - d + 1; open = false; }
-                }
-                // first inside rank is in [bad, good]
-                uint32_t lo = bad, hi = good;
-                while (lo < hi) {
-                    const uint32_t mid = lo + ((hi - lo) >> 1);
-                    if (inside(mid)) { hi = mid; } else { lo = mid + 1; }
-                }
-                q_lo = lo;
-            }
-            uint8_t own_next = best >= (uint32_t)kLenMin ? src[i + best] : (uint8_t)0;   // best < cap: i + best < n
-            for (uint32_t q = q_from; q > q_lo && best < cap; ) {
-                q--;
-                const uint32_t p = S[q];
-                if (best >= (uint32_t)kLenMin && src[p + best] != own_next) { continue; }
-                uint32_t k = 3;
-                while (k < cap) {
-                    if (i + k + 4 <= n) {
-                        const uint32_t x = load_u32_unaligned(src + p + k) ^ load_u32_unaligned(src + i + k);
-                        if (x != 0) { k += (uint32_t)__builtin_ctz(x) >> 3; break; }
-                        k += 4;
-                    } else {
-                        if (src[p + k] != src[i + k]) { break; }
-                        k++;
-                    }
-                }
-                if (k > cap) { k = cap; }
-                if (k > best) {                                // strictly longer: nearest among equals
-                    best = k; dist = i - p;
-                    if (best < cap) { own_next = src[i + best]; }
-                }
-            }
-        };
+        bool later = false;                                  // this lane finishes by itself, from rank `resume` down
+        uint32_t resume = 0;
         const uint32_t key0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
-        if (__ballot(valid && key == key0 && i + 16 <= n) == ~0ull) {
+        if (__ballot(valid && key == key0 && i <= tail) == ~0ull) {
             // ---- the whole wave sits inside one run of equal keys (a frequent 3-byte string) ---
             // Its lanes walk the same candidates, one rank apart.  Walk them ONCE: every lane compares the
             // candidate with its own first 16 bytes, held in registers.  Same order (nearest first), same strict >.
-            bool done = false, deferred = false;
-            uint32_t resume = 0;
+            bool alive = true;
             // page = sorted positions of ranks [page_base, +64) AND their first 16 bytes, one rank per lane: a
             // candidate's position and bytes come out of these registers (v_readlane) -- one gather per 64
             // candidates instead of a dependent load per candidate (each turn of this loop used to wait for it)
             uint32_t page_base = r0, page = i, pb0 = own0, pb1 = own1, pb2 = own2, pb3 = own3;
+            const uint64_t own_lo = ((uint64_t)own1 << 32) | own0, own_hi = ((uint64_t)own3 << 32) | own2;
             for (int64_t c = (int64_t)r0 + kWave - 2; c >= 0; c--) {
                 if (c < (int64_t)page_base) {
                     page_base -= (uint32_t)kWave;            // r0 is a multiple of 64: so is every page
-                    page = S[page_base + (uint32_t)lane];
-                    load16(page, pb0, pb1, pb2, pb3);        // (zeros beyond the stream's end)
+                    page = S[page_base + (uint32_t)lane];    // (every rank of an earlier page exists)
+                    settle16(page, fetch16(page), pb0, pb1, pb2, pb3);
                 }
                 const int at = (int)(c - (int64_t)page_base);
                 const uint32_t pc = (uint32_t)__builtin_amdgcn_readlane((int)page, at);
                 const bool below = (int64_t)r > c;           // the candidate comes before my position
                 const uint32_t d = i - pc;
-                if (below && d > reach) { done = true; }     // everything further is farther
-                if (__ballot(!done) == 0) { break; }
+                alive &= !(below & (d > reach));             // everything further is farther
+                if (__ballot(alive) == 0) { break; }
                 // its key first: a rank in front of the run can be any position
                 const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)pb0, at);
                 if ((c0 & 0x00FFFFFFu) != key0) { break; }   // left the run: so have all earlier ranks
                 const uint32_t c1 = (uint32_t)__builtin_amdgcn_readlane((int)pb1, at);
                 const uint32_t c2 = (uint32_t)__builtin_amdgcn_readlane((int)pb2, at);
                 const uint32_t c3 = (uint32_t)__builtin_amdgcn_readlane((int)pb3, at);
-                const uint32_t x0 = own0 ^ c0, x1 = own1 ^ c1, x2 = own2 ^ c2, x3 = own3 ^ c3;
-                uint32_t len = x0 != 0 ? ((uint32_t)__builtin_ctz(x0) >> 3)
-                             : x1 != 0 ? 4u + ((uint32_t)__builtin_ctz(x1) >> 3)
-                             : x2 != 0 ? 8u + ((uint32_t)__builtin_ctz(x2) >> 3)
-                             : x3 != 0 ? 12u + ((uint32_t)__builtin_ctz(x3) >> 3) : 16u;
-                const bool want = below && !done;
-                if (want && len == 16u && cap > 16u) {       // longer than the registers hold:
-                    deferred = true;                         // this lane goes on by itself from here
-                    resume = (uint32_t)c + 1u;               // (a long compare inside this loop would
-                    done = true;                             // hold up the other 63 lanes)
-                } else {
-                    if (len > cap) { len = cap; }
-                    if (want && len > best) {                // strictly longer: nearest among equals
-                        best = len; dist = d;
-                        if (best >= cap) { done = true; }
-                    }
-                }
+                const uint64_t x_lo = own_lo ^ (((uint64_t)c1 << 32) | c0), x_hi = own_hi ^ (((uint64_t)c3 << 32) | c2);
+                uint32_t len = x_lo != 0 ? ((uint32_t)__builtin_ctzll(x_lo) >> 3)
+                             : x_hi != 0 ? 8u + ((uint32_t)__builtin_ctzll(x_hi) >> 3) : 16u;
+                const bool want = below & alive;
+                // longer than the registers hold: this lane goes on by itself from here (a long compare inside
+                // this loop would hold up the other 63 lanes)
+                const bool full = want & (len == 16u) & (cap > 16u);
+                later |= full;
+                resume = full ? (uint32_t)c + 1u : resume;
+                alive &= !full;
+                len = len > cap ? cap : len;
+                const bool better = want & !full & (len > best);     // strictly longer: nearest among equals
+                best = better ? len : best;
+                dist = better ? d : dist;
+                alive &= best < cap;
                 // a run of long matches (padding, repeated records): nearly every lane ends up on
                 // its own anyway, so stop sharing early instead of trickling them out one per turn
-                if (__builtin_popcountll(__ballot(deferred)) >= kSharedGiveUp) {
-                    if (!done) {
-                        deferred = true;
+                if (__builtin_popcountll(__ballot(later)) >= kSharedGiveUp) {
+                    if (alive) {
+                        later = true;
                         resume = below ? (uint32_t)c : r;    // ranks [c, r) are behind me / nothing is
-                        done = true;
                     }
                     break;
                 }
             }
-            if (deferred) { walk(resume); }
-            M[i] = best >= (uint32_t)kLenMin ? ((best << 16) | dist) : (key & 0xFFu);   // no match: the literal itself
-            prev_i = i; prev0 = own0; prev1 = own1; prev2 = own2; prev3 = own3;
-            continue;
-        }
-        // ---- several runs in one wave (the usual case: 2.7 candidates per position on Zipf bytes) ------
-        // The candidates of rank r are the ranks r-1, r-2, ... of its run, nearest first -- and those are
-        // the positions the NEIGHBOURING LANES hold, in this page or in the one before it (kept from the
-        // previous turn of the loop).  A candidate's position and bytes come out of lane l-k's registers
-        // through the LDS crossbar (ds_bpermute): no gather and no dependent load per candidate (a lane that
-        // walks by itself pays three dependent global loads per candidate, and one such lane holds up its
-        // wave: with per-lane walks the kernel ran at 13 us per page).  Same order, same strict >.  What the
-        // registers cannot settle leaves the loop and is finished by the lane itself with walk(): a match
-        // longer than the 16 bytes held, and a run that reaches back more than 64 ranks.
-        bool done = !valid;
-        bool later = false;                                      // this lane finishes by itself, from rank `resume` down
-        uint32_t resume = 0;
-        for (int k = 1; k <= kWave; k++) {
-            const int from = lane - k;
-            const bool in_cur = from >= 0;
-            if (!done && !in_cur && !have_prev) { done = true; }  // nothing lies in front of rank 0
-            if (__ballot(!done) == 0) { break; }
-            const int addr = (from & (kWave - 1)) << 2;
-            uint32_t pc = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)i);
-            uint32_t c0 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)own0);
-            uint32_t c1 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)own1);
-            const bool back = __ballot(!done && !in_cur) != 0;   // someone looks into the page before
-            if (back) {
-                const uint32_t qc = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev_i);
-                const uint32_t q0 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev0);
-                const uint32_t q1 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev1);
-                pc = in_cur ? pc : qc; c0 = in_cur ? c0 : q0; c1 = in_cur ? c1 : q1;
-            }
-            const uint32_t x0 = own0 ^ c0, x1 = own1 ^ c1;
-            if (!done && (x0 & 0x00FFFFFFu) != 0) { done = true; }           // left the run: so have all earlier ranks
-            const uint32_t d = i - pc;
-            if (!done && d > reach) { done = true; }                        // everything further is farther
-            uint32_t len = x0 != 0 ? ((uint32_t)__builtin_ctz(x0) >> 3) : x1 != 0 ? 4u + ((uint32_t)__builtin_ctz(x1) >> 3) : 8u;
-            if (__ballot(!done && len == 8u && cap > 8u) != 0) {             // (rare on Zipf bytes: the other two words)
-                uint32_t c2 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)own2);
-                uint32_t c3 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)own3);
+        } else {
+            // ---- several runs in one wave (the usual case: 2.7 candidates per position on Zipf bytes) ------
+            // The candidates of rank r are the ranks r-1, r-2, ... of its run, nearest first -- and those are
+            // the positions the NEIGHBOURING LANES hold, in this page or in the one before it (kept from the
+            // previous turn of the loop).  A candidate's position and bytes come out of lane l-k's registers
+            // through the LDS crossbar (ds_bpermute): no gather and no dependent load per candidate (a lane that
+            // walks by itself pays three dependent global loads per candidate, and one such lane holds up its
+            // wave: with per-lane walks the kernel ran at 13 us per page).  Same order, same strict >.  What the
+            // registers cannot settle leaves the loop and is finished by the lane itself with walk(): a match
+            // longer than the 16 bytes held, and a run that reaches back more than 64 ranks.
+            // A turn is branch-free but for three wave-uniform branches: the lane's state is ONE predicate,
+            // `alive`, that conditions are and-ed into, and every update is a select.
+            bool alive = valid;
+            const uint64_t own_lo = ((uint64_t)own1 << 32) | own0;
+            for (int k = 1; k <= kWave; k++) {
+                const int from = lane - k;
+                const bool in_cur = from >= 0;
+                alive &= in_cur | have_prev;                         // nothing lies in front of rank 0
+                if (__ballot(alive) == 0) { break; }
+                const int addr = (from & (kWave - 1)) << 2;
+                uint32_t pc = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)i);
+                uint32_t c0 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)own0);
+                uint32_t c1 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)own1);
+                const bool back = __ballot(alive & !in_cur) != 0;    // someone looks into the page before
                 if (back) {
-                    const uint32_t q2 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev2);
-                    const uint32_t q3 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev3);
-                    c2 = in_cur ? c2 : q2; c3 = in_cur ? c3 : q3;
+                    const uint32_t qc = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev_i);
+                    const uint32_t q0 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev0);
+                    const uint32_t q1 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev1);
+                    pc = in_cur ? pc : qc; c0 = in_cur ? c0 : q0; c1 = in_cur ? c1 : q1;
                 }
-                const uint32_t x2 = own2 ^ c2, x3 = own3 ^ c3;
-                if (len == 8u) {
-                    len = x2 != 0 ? 8u + ((uint32_t)__builtin_ctz(x2) >> 3) : x3 != 0 ? 12u + ((uint32_t)__builtin_ctz(x3) >> 3) : 16u;
-                }
-            }
-            if (!done) {
-                if (len == 16u && cap > 16u) {                   // longer than the registers hold: this lane goes on
-                    later = true;                                // by itself, starting with this very candidate
-                    resume = r - (uint32_t)k + 1u;
-                    done = true;
-                } else {
-                    if (len > cap) { len = cap; }
-                    if (len > best) {                            // strictly longer: nearest among equals
-                        best = len; dist = d;
-                        if (best >= cap) { done = true; }
+                const uint64_t x = own_lo ^ (((uint64_t)c1 << 32) | c0);
+                const uint32_t d = i - pc;
+                // left the run (so have all earlier ranks) or out of reach (everything further is farther)
+                alive &= (((uint32_t)x & 0x00FFFFFFu) == 0u) & (d <= reach);
+                uint32_t len = x != 0 ? ((uint32_t)__builtin_ctzll(x) >> 3) : 8u;
+                if (__ballot(alive & (len == 8u) & (cap > 8u)) != 0) {      // (rare on Zipf bytes: the other two words)
+                    uint32_t c2 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)own2);
+                    uint32_t c3 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)own3);
+                    if (back) {
+                        const uint32_t q2 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev2);
+                        const uint32_t q3 = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)prev3);
+                        c2 = in_cur ? c2 : q2; c3 = in_cur ? c3 : q3;
                     }
-                    if (!done && k == kWave) {                   // 64 ranks back and still inside the run
-                        later = true;
-                        resume = r - (uint32_t)kWave;
-                        done = true;
-                    }
+                    const uint64_t x_hi = (((uint64_t)own3 << 32) | own2) ^ (((uint64_t)c3 << 32) | c2);
+                    const uint32_t more = x_hi != 0 ? 8u + ((uint32_t)__builtin_ctzll(x_hi) >> 3) : 16u;
+                    len = len == 8u ? more : len;
                 }
+                // longer than the registers hold: this lane goes on by itself, starting with this very candidate
+                const bool full = alive & (len == 16u) & (cap > 16u);
+                later |= full;
+                resume = full ? r - (uint32_t)k + 1u : resume;
+                alive &= !full;
+                len = len > cap ? cap : len;
+                const bool better = alive & (len > best);            // strictly longer: nearest among equals
+                best = better ? len : best;
+                dist = better ? d : dist;
+                alive &= best < cap;
             }
+            // (the loop ran out with the lane still looking) 64 ranks back and still inside the run
+            resume = alive ? r - (uint32_t)kWave : resume;
+            later |= alive;
         }
-        if (later) { walk(resume); }
-        if (valid) { M[i] = best >= (uint32_t)kLenMin ? ((best << 16) | dist) : (key & 0xFFu); }   // no match: the literal itself
+        MATCH_SEC(sec, 1)
+        if (later) { walk(resume, i, key, cap, reach, best, dist); }
+        MATCH_SEC(sec, 2)
+        // no match: the literal itself.  A lane without a rank holds the last rank's position: it stores that
+        // rank's word there again.
+        const uint32_t word = best >= (uint32_t)kLenMin ? ((best << 16) | dist) : (key & 0xFFu);
+        const uint32_t ranks = count - r0;                   // of this page, if fewer than 64
+        const uint32_t last_word = (uint32_t)__builtin_amdgcn_readlane((int)word, (int)(ranks < (uint32_t)kWave ? ranks - 1u : (uint32_t)kWave - 1u));
+        M[i] = valid ? word : last_word;
+        MATCH_SEC(sec, 3)
         prev_i = i; prev0 = own0; prev1 = own1; prev2 = own2; prev3 = own3;
+    };
+
+    // ---- the pipeline: positions two pages ahead, bytes one page ahead ---------------------------------------
+    uint32_t pos_cur = fetch_pos(page_lo);
+    uint32_t pos_nxt = fetch_pos(page_lo + 1u);
+    if (page_lo > 0) {                                       // (every rank of an earlier page exists)
+        prev_i = S[(page_lo - 1u) * (uint32_t)kWave + (uint32_t)lane];
+        settle16(prev_i, fetch16(prev_i), prev0, prev1, prev2, prev3);
     }
+    U128u got_cur = fetch16(pos_cur);
+    {   // the first page, apart from the loop: nothing of a page before it is in flight
+        const uint32_t pos_far = fetch_pos(page_lo + 2u);
+        const U128u got_nxt = fetch16(pos_nxt);
+        uint32_t own0, own1, own2, own3;
+        settle16(pos_cur, got_cur, own0, own1, own2, own3);
+        do_page(page_lo, pos_cur, own0, own1, own2, own3);
+        pos_cur = pos_nxt; pos_nxt = pos_far; got_cur = got_nxt;
+    }
+    for (uint32_t pg = page_lo + 1u; pg < page_hi; pg++) {
+        // in flight here, oldest first: pos_nxt (page pg + 1), got_cur (page pg), the store of page pg - 1
+        const uint32_t pos_far = fetch_pos(pg + 2u);
+        const U128u got_nxt = fetch16(pos_nxt);              // waits for pos_nxt: two operations behind it
+        uint32_t own0, own1, own2, own3;
+        settle16(pos_cur, got_cur, own0, own1, own2, own3);  // waits for got_cur: three operations behind it
+        do_page(pg, pos_cur, own0, own1, own2, own3);
+        pos_cur = pos_nxt; pos_nxt = pos_far; got_cur = got_nxt;
+    }
+#ifdef SQZ_STATS
+    if (threadIdx.x == 0 && b == 1 && group == 0) {
+        printf("match block 1: cycles %llu: loads %llu candidates %llu own_walks %llu store %llu\n",
+               (unsigned long long)(sec.last - sec_begin), (unsigned long long)sec.t[0], (unsigned long long)sec.t[1],
+               (unsigned long long)sec.t[2], (unsigned long long)sec.t[3]);
+    }
+#endif
 }
 
 // ---------------------------------------------------------------------------
