@@ -569,8 +569,10 @@ SQZ_API int sqz_hip_lz77_blocks_dict(const void* d_in, const uint64_t* d_in_off,
  * reader first compares dict_bytes and the CRC-32 of the dictionary it was given with the record: a mismatch is
  * EILSEQ for the call and for every block (block_err), nothing is decoded and nothing is written; a frame of
  * version 1 or 2 is EINVAL.  sqz_frame_decompress and sqz_frame_read answer EINVAL for a version-3 frame.
- * The device-resident flavour does not know version 3 yet: sqz_hip_frame_encode* with SQZ_FRAME_DICT are EINVAL,
- * and sqz_hip_frame_decode refuses a version-3 frame by arithmetic (*d_status = EINVAL, nothing decoded).   */
+ * The device-resident calls above keep to versions 1 and 2: sqz_hip_frame_encode* with SQZ_FRAME_DICT are EINVAL,
+ * sqz_hip_frame_scratch_bytes_ex answers 0 for it, and sqz_hip_frame_decode refuses a version-3 frame by arithmetic
+ * (*d_status = EINVAL, nothing decoded).  Version 3 on the device has calls of its own, further down:
+ * sqz_hip_frame_encode_dict, sqz_hip_frame_decode_dict, sqz_hip_frame_read_dict.                             */
 SQZ_API int sqz_frame_dict(const uint8_t* frame, uint64_t avail, uint32_t* dict_bytes, uint32_t* dict_crc);
 SQZ_API uint64_t sqz_frame_bound_dict(uint64_t content_bytes, uint32_t block_bits, uint32_t flags);
 SQZ_API int sqz_frame_compress_dict(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
@@ -580,6 +582,60 @@ SQZ_API int sqz_frame_decompress_dict(const uint8_t* frame, uint64_t avail, cons
                                       uint8_t* data, uint64_t capacity, uint64_t* bytes, int32_t* block_err);
 SQZ_API int sqz_frame_read_dict(const uint8_t* frame, uint64_t avail, const uint8_t* dict, uint64_t dict_bytes,
                                 uint64_t offset, uint64_t length, uint8_t* out);
+
+/* Version 3 in the device-resident flavour, and ranged reads from a frame that is already in device memory.  Every
+ * pointer a DEVICE pointer (d_frame and d_scratch 16-byte aligned), asynchronous, no host synchronisation inside;
+ * d_frame_bytes, d_status, d_err as for sqz_hip_frame_encode / sqz_hip_frame_decode.  Call-level EINVAL, before the
+ * device is touched: d_dict == NULL, dict_bytes == 0, dict_bytes > window - 1 (encode) or > 32767 (decode, read), a
+ * parse that is none, flags other than SQZ_FRAME_STORED and SQZ_FRAME_DICT, misaligned d_frame / d_scratch.
+ *
+ * encode_dict: flags 0 or SQZ_FRAME_STORED, with or without SQZ_FRAME_DICT, which is set in the header either way
+ *   (sqz_frame_compress_dict's rule).  Always the indexed finder.  The dictionary is sorted once per call in the
+ *   scratch, and its CRC-32 for the record is computed on the device.  The frame equals sqz_frame_compress_dict's
+ *   byte for byte and fits sqz_frame_bound_dict.  Scratch:
+ *       sqz_hip_frame_scratch_bytes_dict(c, b, 1, flags, D) = sqz_hip_frame_scratch_bytes_ex(c, b, 1, flags & SQZ_FRAME_STORED)
+ *                                                             + 256 + 2 * round_up_256(4 * (D + 64))
+ *       sqz_hip_frame_scratch_bytes_dict(c, b, 0, flags, D) = sqz_hip_frame_scratch_bytes(c, b, 0)
+ *   and 0 for a block_bits outside 12..24, any other flag, or D outside 1..32767.
+ * decode_dict: avail must cover header, index and record, 32 + 8 n + 8 bytes (E2BIG at the call otherwise).  A kernel
+ *   checks, in this order: magic, version 3 with flags bit 1 and none of bits 2..7, field ranges (EINVAL; so a
+ *   frame of version 1 or 2 is EINVAL here); the header against n_blocks and content_bytes (EINVAL); index_crc over
+ *   [0,28), index and record (EILSEQ); the record's dict_bytes in 1 .. window - 1 (EINVAL); stored entries only with
+ *   bit 0 and of their block's size (EINVAL); the words' sum against payload_bytes (EINVAL); the record against
+ *   dict_bytes and the CRC-32 of d_dict, computed by a kernel just before (EILSEQ); the payload inside avail (E2BIG).
+ *   On any of these *d_status and every d_err[b] get that value and d_out is not written: a wrong dictionary
+ *   decodes nothing.  Otherwise d_err[b] as for sqz_frame_decompress_dict.
+ * read / read_dict: content[offset, offset + length) of a resident frame of versions 1 and 2 / of version 3 into
+ *   d_out.  n_blocks, content_bytes and block_bits are what sqz_frame_info said about a host copy of the 32 header
+ *   bytes; the host works out the covering blocks, first = offset >> block_bits, from them.  EINVAL at the call: the
+ *   range leaves the content, block_bits outside 12..24, n_blocks != ceil(content_bytes / 2^block_bits).  The
+ *   covering blocks are decoded into the scratch and verified, d_err has ONE ENTRY PER COVERING BLOCK, and
+ *   *d_status = the frame's status (the checks of sqz_hip_frame_decode / _decode_dict; EINVAL also for a frame whose
+ *   block_bits is another), otherwise the first non-zero d_err.  d_out receives exactly `length` bytes when
+ *   *d_status == 0 and is not written otherwise: a covering block that fails its decode or its checksum delivers
+ *   nothing; a damaged block outside the range does not matter.  length == 0 sets *d_status = 0 on the stream and
+ *   launches nothing else.  As for the decode calls the WHOLE frame, not only the covering streams, must lie inside
+ *   avail (E2BIG in *d_status otherwise).  Scratch, the same for both calls, the worst case over every offset:
+ *       sqz_hip_frame_read_scratch_bytes(length, b) = sqz_hip_frame_scratch_bytes(k << b, b, 0)
+ *                                                     + round_up_256((k << b) + 16) + 256
+ *       with k = ((length + 2^b - 2) >> b) + 1 covering blocks (k = 0 for length == 0); 0 for a bad block_bits.   */
+SQZ_API uint64_t sqz_hip_frame_scratch_bytes_dict(uint64_t content_bytes, uint32_t block_bits, int encode,
+                                                  uint32_t flags, uint64_t dict_bytes);
+SQZ_API int sqz_hip_frame_encode_dict(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
+                                      uint32_t flags, uint32_t parse, const void* d_dict, uint64_t dict_bytes,
+                                      void* d_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
+                                      int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API int sqz_hip_frame_decode_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                      const void* d_dict, uint64_t dict_bytes, void* d_out, int32_t* d_err,
+                                      int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API uint64_t sqz_hip_frame_read_scratch_bytes(uint64_t length, uint32_t block_bits);
+SQZ_API int sqz_hip_frame_read(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                               uint32_t block_bits, uint64_t offset, uint64_t length, void* d_out, int32_t* d_err,
+                               int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API int sqz_hip_frame_read_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                    uint32_t block_bits, uint64_t offset, uint64_t length, const void* d_dict,
+                                    uint64_t dict_bytes, void* d_out, int32_t* d_err, int32_t* d_status,
+                                    void* d_scratch, uint64_t scratch_bytes, void* stream);
 
 /* Live timing of the last kernels enqueued through this library on the
  * calling thread's context, measured with HIP events ON THE LAUNCH STREAM.

@@ -168,6 +168,16 @@ PROTOTYPES = {
                                           C.c_uint64, _vp, C.c_uint64, _u64p]),
     "sqz_frame_decompress_dict": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
     "sqz_frame_read_dict": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp]),
+    "sqz_hip_frame_scratch_bytes_dict": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64]),
+    "sqz_hip_frame_encode_dict": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                            C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_frame_decode_dict": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp,
+                                            _vp, C.c_uint64, _vp]),
+    "sqz_hip_frame_read_scratch_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "sqz_hip_frame_read": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, _vp,
+                                     _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_frame_read_dict": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
+                                          _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
     "sqz_hip_set_finder": (None, [C.c_int]),
     "sqz_hip_get_finder": (C.c_int, []),
     "sqz_hip_set_timing": (None, [C.c_int]),

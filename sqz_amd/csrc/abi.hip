@@ -582,7 +582,9 @@ FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_byt
     L.in_off = take((n + 1) * 8);
     L.out_off = take((n + 1) * 8);                          // encode: the slabs' offsets
     L.crc = take(n * 4 + 4);
-    L.misc = take(256);                                     // [0,16) the index's range, [16,20) its checksum, [32,48) spare
+    L.misc = take(256);                                     // [0,16) the index's range, [16,20) its checksum, [32,48) spare;
+                                                            // version 3: [64,80) the dictionary's range, [96,112) spare,
+                                                            // [128,132) the dictionary's checksum
     if (encode) {
         L.out_bytes = take(n * 8);
         L.copy_bytes = take(n * 8);
@@ -602,15 +604,19 @@ FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_byt
 int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
                      uint8_t* d_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
                      int32_t* d_err, uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t flags = 0,
-                     uint32_t parse = SQZ_PARSE_GREEDY) {
+                     uint32_t parse = SQZ_PARSE_GREEDY, const uint8_t* d_dict = nullptr, uint32_t dict_bytes = 0) {
     const uint64_t bb = 1ull << block_bits, n64 = frame_blocks(content_bytes, block_bits);
     if (n64 > 0xFFFFFFFFull) { return EINVAL; }
     const uint32_t n = (uint32_t)n64;
     const uint64_t slab = sqz_bound(bb);
     const bool store = (flags & SQZ_FRAME_STORED) != 0;
     const FrameScratch L = frame_scratch(n, content_bytes, slab, true, store);
+    // version 3: the dictionary's index lies in front of everything else, as in sqz_hip_encode_blocks_dict
+    const uint64_t dict_area = d_dict != nullptr ? dict_index_bytes(dict_bytes) : 0;
+    if (scratch_bytes < dict_area + L.total) { return EINVAL; }
+    uint8_t* const dict_idx = scratch;
+    scratch += dict_area;
     uint32_t* stored = (uint32_t*)(scratch + L.stored);
-    if (scratch_bytes < L.total) { return EINVAL; }
     uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
     uint64_t* slab_off = (uint64_t*)(scratch + L.out_off);
     uint64_t* out_bytes = (uint64_t*)(scratch + L.out_bytes);
@@ -619,7 +625,14 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
     uint32_t* crc = (uint32_t*)(scratch + L.crc);
     uint64_t* idx_off = (uint64_t*)(scratch + L.misc);
     uint32_t* idx_crc = (uint32_t*)(scratch + L.misc + 16);
+    uint32_t* dict_crc = (uint32_t*)(scratch + L.misc + 128);
     sqzk::launch_frame_plan(n, bb, content_bytes, slab, in_off, slab_off, st);
+    DictDev dd;
+    if (d_dict != nullptr) {                                // sorted once per call; its checksum over the sort's own
+        dd = run_dict_index(d_dict, dict_bytes, dict_idx, st);  // range {0, D}, for the record
+        SpanGuard g(st, SQZ_HIP_K_CRC32);
+        sqzk::launch_crc32_blocks(d_dict, (const uint64_t*)dict_idx, 1, dict_crc, dict_bytes, st);
+    }
     if (n > 0) {
         { SpanGuard g(st, SQZ_HIP_K_CRC32);
           sqzk::launch_crc32_blocks(d_in, in_off, n, crc, bb, st); }
@@ -627,20 +640,26 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
         const uint64_t slots = (L.codec_bytes - head) / 8;
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + head);
-        run_encode(finder_for(parse), d_in, in_off, n, 1u << win_bits, tokens, counts, tokens, tokens + slots, bb,
-                   scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st, parse);
+        run_encode(d_dict != nullptr ? 1 : finder_for(parse), d_in, in_off, n, 1u << win_bits, tokens, counts, tokens,
+                   tokens + slots, bb, scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st, parse,
+                   d_dict != nullptr ? &dd : nullptr);
     }
     { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
-      if (store) {
+      if (d_dict != nullptr) {
+          sqzk::launch_frame_index_v3(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, flags, dict_bytes,
+                                      dict_crc, d_frame, capacity, copy_bytes, dense_off, stored, idx_off,
+                                      d_frame_bytes, d_status, st);
+      } else if (store) {
           sqzk::launch_frame_index_v2(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, d_frame, capacity,
                                       copy_bytes, dense_off, stored, idx_off, d_frame_bytes, d_status, st);
       } else {
           sqzk::launch_frame_index(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, d_frame, capacity,
                                    copy_bytes, dense_off, idx_off, d_frame_bytes, d_status, st);
       } }
+    const uint32_t record = d_dict != nullptr ? 8 : 0;
     { SpanGuard g(st, SQZ_HIP_K_CRC32);
-      sqzk::launch_crc32_blocks(d_frame, idx_off, 1, idx_crc, 8 * (uint64_t)n, st); }
-    sqzk::launch_frame_seal(d_frame, idx_crc, n, d_status, st);
+      sqzk::launch_crc32_blocks(d_frame, idx_off, 1, idx_crc, 8 * (uint64_t)n + record, st); }
+    sqzk::launch_frame_seal(d_frame, idx_crc, n, d_status, st, record);
     if (n > 0) {
         sqzk::launch_compact_blocks(scratch + L.slabs, slab_off, copy_bytes, n, d_frame, dense_off, bb / 2, st);
         if (store) {                                        // the stored blocks' content, where the index says
@@ -674,9 +693,11 @@ void run_frame_decode(const uint8_t* d_in, const uint64_t* in_off, const uint64_
 // the device side of a frame decode, blocks [first, first + n_sel) into d_out (block `first` at its start)
 int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_t content_bytes, uint32_t first,
                      uint32_t n_sel, uint64_t sel_bytes, uint8_t* d_out, int32_t* d_err, int32_t* d_status,
-                     uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t version) {
+                     uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t version,
+                     const uint8_t* d_dict = nullptr, uint32_t dict_bytes = 0, uint32_t want_bits = 0) {
     const FrameScratch L = frame_scratch(n_sel, sel_bytes, 0, false);
-    if (scratch_bytes < L.total || avail < 32 + 8 * (uint64_t)n) { return scratch_bytes < L.total ? EINVAL : E2BIG; }
+    const uint64_t record = d_dict != nullptr ? 8 : 0;      // a dictionary: the version-3 reader, and no other
+    if (scratch_bytes < L.total || avail < 32 + 8 * (uint64_t)n + record) { return scratch_bytes < L.total ? EINVAL : E2BIG; }
     uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
     uint64_t* out_off = (uint64_t*)(scratch + L.out_off);
     uint32_t* crc = (uint32_t*)(scratch + L.crc);
@@ -684,13 +705,28 @@ int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_
     uint64_t* idx_off = (uint64_t*)(scratch + L.misc);
     uint32_t* idx_crc = (uint32_t*)(scratch + L.misc + 16);
     uint64_t* spare = (uint64_t*)(scratch + L.misc + 32);
-    // {0, 8 n}: the index as one range behind the header, written on the device (no host copy to wait for)
-    sqzk::launch_frame_plan(1, 8 * (uint64_t)n, 8 * (uint64_t)n, 0, idx_off, spare, st);
+    // {0, 8 n}: the index as one range behind the header, written on the device (no host copy to wait for);
+    // with the record of a version-3 frame {0, 8 n + 8}
+    const uint64_t idx_bytes = 8 * (uint64_t)n + record;
+    sqzk::launch_frame_plan(1, idx_bytes, idx_bytes, 0, idx_off, spare, st);
     { SpanGuard g(st, SQZ_HIP_K_CRC32);
-      sqzk::launch_crc32_blocks(d_frame + 32, idx_off, 1, idx_crc, 8 * (uint64_t)n, st); }
-    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
-      sqzk::launch_frame_open_v2(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, in_off, out_off, stored,
-                                 d_status, st); }
+      sqzk::launch_crc32_blocks(d_frame + 32, idx_off, 1, idx_crc, idx_bytes, st); }
+    DictDev dd;
+    if (d_dict != nullptr) {                                // the checksum of what the caller brought, for the open kernel
+        uint64_t* dict_off = (uint64_t*)(scratch + L.misc + 64);        // [64,80) {0, D}, [96,112) spare, [128,132) its crc
+        uint32_t* dict_crc = (uint32_t*)(scratch + L.misc + 128);
+        sqzk::launch_frame_plan(1, dict_bytes, dict_bytes, 0, dict_off, dict_off + 4, st);
+        { SpanGuard g(st, SQZ_HIP_K_CRC32);
+          sqzk::launch_crc32_blocks(d_dict, dict_off, 1, dict_crc, dict_bytes, st); }
+        SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+        sqzk::launch_frame_open_v3(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, dict_bytes, dict_crc, in_off,
+                                   out_off, stored, d_status, st, want_bits);
+        dd.bytes = d_dict; dd.len = dict_bytes;
+    } else {
+        SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+        sqzk::launch_frame_open_v2(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, in_off, out_off, stored,
+                                   d_status, st, want_bits);
+    }
     // version: what a host copy of the header said, 0 when the caller has none (the device flavour).  Only a frame
     // known to be version 1 goes without the mask, and then without the copy launch
     const uint32_t* const skip = version == 1 ? nullptr : stored;
@@ -698,9 +734,45 @@ int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + align_up((uint64_t)n_sel * 4, 256));
         run_frame_decode(d_frame, in_off, out_off, n_sel, (sel_bytes + n_sel - 1) / n_sel, tokens, counts, d_out, d_err,
-                         skip, stored, crc, DictDev(), st);
+                         skip, stored, crc, dd, st);
         sqzk::launch_frame_verify(d_frame, first, n_sel, crc, d_status, d_err, st);
     }
+    return hip_errno(hipGetLastError());
+}
+
+// where the pieces of a ranged read's scratch lie: the decode's scratch for the covering blocks, the blocks
+// themselves, the copy's work list
+struct ReadScratch { FrameScratch dec; uint64_t blocks, plan, total; };
+ReadScratch read_scratch(uint64_t n_sel, uint64_t sel_bytes) {
+    ReadScratch R;
+    R.dec = frame_scratch(n_sel, sel_bytes, 0, false);
+    R.blocks = R.dec.total;
+    R.plan = R.blocks + align_up(sel_bytes + 16, 256);
+    R.total = R.plan + 256;
+    return R;
+}
+
+// the device side of a ranged read: the covering blocks into the scratch (frame_decode_dev), then status and work
+// list (frame_read_plan_kernel), then the range or nothing into d_out (range_copy_kernel).  The caller has checked
+// the range against content_bytes and n against block_bits; length > 0
+int frame_read_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_t content_bytes, uint32_t block_bits,
+                   uint64_t offset, uint64_t length, uint8_t* d_out, int32_t* d_err, int32_t* d_status,
+                   uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, const uint8_t* d_dict, uint32_t dict_bytes) {
+    const uint64_t bb = 1ull << block_bits;
+    const uint64_t first = offset >> block_bits, b_end = ((offset + length - 1) >> block_bits) + 1;
+    const uint64_t n_sel = b_end - first;
+    const uint64_t sel_bytes = (b_end * bb < content_bytes ? b_end * bb : content_bytes) - first * bb;
+    const ReadScratch R = read_scratch(n_sel, sel_bytes);
+    if (scratch_bytes < R.total) { return EINVAL; }
+    uint8_t* const blocks = scratch + R.blocks;
+    uint64_t* const plan = (uint64_t*)(scratch + R.plan);
+    const int e = frame_decode_dev(d_frame, avail, n, content_bytes, (uint32_t)first, (uint32_t)n_sel, sel_bytes, blocks,
+                                   d_err, d_status, scratch, R.dec.total, st, 0, d_dict, dict_bytes, block_bits);
+    if (e != 0) { return e; }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frame_read_plan(d_err, (uint32_t)n_sel, offset - first * bb, length, plan, d_status, st); }
+    { SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+      sqzk::launch_range_copy(blocks, plan, d_out, plan + 2, plan + 2, (const uint32_t*)(plan + 4), 1, false, length, st); }
     return hip_errno(hipGetLastError());
 }
 
@@ -1916,6 +1988,94 @@ int sqz_hip_frame_decode(const void* d_frame, uint64_t avail, uint32_t n_blocks,
     return frame_decode_dev((const uint8_t*)d_frame, avail, n_blocks, content_bytes, 0, n_blocks, content_bytes,
                             (uint8_t*)d_out, d_err, d_status, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
                             0);
+}
+
+// ---- version 3 in the device-resident flavour, and ranged reads from a resident frame
+static bool frame_dict_flags_ok(uint32_t flags) { return (flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_DICT)) == 0; }
+
+uint64_t sqz_hip_frame_scratch_bytes_dict(uint64_t content_bytes, uint32_t block_bits, int encode, uint32_t flags,
+                                          uint64_t dict_bytes) {
+    if (!frame_dict_flags_ok(flags) || dict_bytes < 1 || dict_bytes > (uint64_t)sqzk_max_window - 1) { return 0; }
+    const uint64_t plain = sqz_hip_frame_scratch_bytes_ex(content_bytes, block_bits, encode,
+                                                          encode != 0 ? flags & (uint32_t)SQZ_FRAME_STORED : 0u);
+    if (plain == 0) { return 0; }
+    return encode != 0 ? plain + dict_index_bytes(dict_bytes) : plain;
+}
+
+int sqz_hip_frame_encode_dict(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
+                              uint32_t flags, uint32_t parse, const void* d_dict, uint64_t dict_bytes, void* d_frame,
+                              uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err,
+                              void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!parse_ok(parse) || !frame_dict_flags_ok(flags) || !frame_params_ok(win_bits, block_bits) ||
+        !dict_ok(d_dict, dict_bytes, 1u << win_bits)) { return EINVAL; }
+    if ((d_in == NULL && content_bytes > 0) || d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 ||
+        d_frame_bytes == NULL || d_status == NULL || (d_err == NULL && content_bytes > 0) || d_scratch == NULL ||
+        ((uintptr_t)d_scratch & 15u) != 0) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    return frame_encode_dev((const uint8_t*)d_in, content_bytes, win_bits, block_bits, (uint8_t*)d_frame, capacity,
+                            d_frame_bytes, d_status, d_err, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
+                            flags & (uint32_t)SQZ_FRAME_STORED, parse, (const uint8_t*)d_dict, (uint32_t)dict_bytes);
+}
+
+int sqz_hip_frame_decode_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                              const void* d_dict, uint64_t dict_bytes, void* d_out, int32_t* d_err, int32_t* d_status,
+                              void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!dict_ok(d_dict, dict_bytes, (uint32_t)sqzk_max_window)) { return EINVAL; }
+    if (d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 || d_status == NULL || d_scratch == NULL ||
+        ((uintptr_t)d_scratch & 15u) != 0 || (n_blocks > 0 && (d_out == NULL || d_err == NULL)) ||
+        (n_blocks == 0) != (content_bytes == 0) || content_bytes / (1ull << sqz_frame_min_block_bits) + 1 < n_blocks) {
+        return EINVAL;
+    }
+    if (avail < 32 + 8 * (uint64_t)n_blocks + 8) { return E2BIG; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    return frame_decode_dev((const uint8_t*)d_frame, avail, n_blocks, content_bytes, 0, n_blocks, content_bytes,
+                            (uint8_t*)d_out, d_err, d_status, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
+                            0, (const uint8_t*)d_dict, (uint32_t)dict_bytes);
+}
+
+uint64_t sqz_hip_frame_read_scratch_bytes(uint64_t length, uint32_t block_bits) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits) { return 0; }
+    const uint64_t bb = 1ull << block_bits;
+    if (length > ~(uint64_t)0 / 8 - 2 * bb) { return 0; }
+    // a range that starts at a block's last byte covers the most blocks
+    const uint64_t n = length == 0 ? 0 : ((length + bb - 2) >> block_bits) + 1;
+    return read_scratch(n, n * bb).total;
+}
+
+// dict == NULL: versions 1 and 2 (sqz_hip_frame_read); else version 3
+static int frame_read_call(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                           uint32_t block_bits, uint64_t offset, uint64_t length, const void* d_dict,
+                           uint64_t dict_bytes, void* d_out, int32_t* d_err, int32_t* d_status, void* d_scratch,
+                           uint64_t scratch_bytes, void* stream) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        frame_blocks(content_bytes, block_bits) != n_blocks || offset > content_bytes ||
+        length > content_bytes - offset) { return EINVAL; }
+    if (d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 || d_status == NULL || d_scratch == NULL ||
+        ((uintptr_t)d_scratch & 15u) != 0 || (length > 0 && (d_out == NULL || d_err == NULL))) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    if (length == 0) { return hip_errno(hipMemsetAsync(d_status, 0, 4, (hipStream_t)stream)); }
+    return frame_read_dev((const uint8_t*)d_frame, avail, n_blocks, content_bytes, block_bits, offset, length,
+                          (uint8_t*)d_out, d_err, d_status, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
+                          (const uint8_t*)d_dict, (uint32_t)dict_bytes);
+}
+
+int sqz_hip_frame_read(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                       uint32_t block_bits, uint64_t offset, uint64_t length, void* d_out, int32_t* d_err,
+                       int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return frame_read_call(d_frame, avail, n_blocks, content_bytes, block_bits, offset, length, NULL, 0, d_out, d_err,
+                           d_status, d_scratch, scratch_bytes, stream);
+}
+
+int sqz_hip_frame_read_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                            uint32_t block_bits, uint64_t offset, uint64_t length, const void* d_dict,
+                            uint64_t dict_bytes, void* d_out, int32_t* d_err, int32_t* d_status, void* d_scratch,
+                            uint64_t scratch_bytes, void* stream) {
+    if (!dict_ok(d_dict, dict_bytes, (uint32_t)sqzk_max_window)) { return EINVAL; }
+    return frame_read_call(d_frame, avail, n_blocks, content_bytes, block_bits, offset, length, d_dict, dict_bytes,
+                           d_out, d_err, d_status, d_scratch, scratch_bytes, stream);
 }
 
 int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t* d_crc, void* stream) {

@@ -118,6 +118,7 @@ __device__ __forceinline__ uint32_t crc32_small(const uint8_t* p, uint32_t n) {
 
 // SQZF version 2 (include/sqz/sqz.h): flags bit 0, bit 31 of an index entry's first word
 constexpr uint32_t kFrameStored = 1u;
+constexpr uint32_t kFrameDict = 2u;                // version 3: flags bit 1, and the record behind the index
 constexpr uint32_t kStoredBit = 0x80000000u;
 
 // content bytes of block b
@@ -269,13 +270,20 @@ void launch_frame_plan(uint32_t n_blocks, uint64_t block_bytes, uint64_t content
 // takes round_up_8(length) bytes of the payload in the same scan, gets copy_bytes[b] = 0 (the compaction passes
 // it by) and stored[b] = 1 (range_copy_kernel moves its content); stored[] is all zeros on a refusal.  With
 // flags = 0 stored is not touched and may be null.
-__global__ __launch_bounds__(256)
-void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
-                        const uint32_t* __restrict__ crc, uint32_t n_blocks, uint64_t content_bytes,
-                        uint32_t win_bits, uint32_t block_bits, uint8_t* __restrict__ frame, uint64_t capacity,
-                        uint64_t* __restrict__ copy_bytes, uint64_t* __restrict__ dense_off,
-                        uint64_t* __restrict__ idx_off, uint64_t* __restrict__ frame_bytes_out,
-                        int32_t* __restrict__ status_out, uint32_t flags, uint32_t* __restrict__ stored) {
+//
+// kDict (flags has SQZ_FRAME_DICT, with or without SQZ_FRAME_STORED) writes version 3: the record { dict_bytes,
+// *dict_crc } directly behind the n entries, payload_off = pad16(32 + 8n + 8) -- the padding now falls on even n --
+// and idx_off = {32, 32 + 8n + 8}, so that the index checksum covers the record.  dict_crc is read on the device:
+// crc32_blocks_kernel over the dictionary wrote it earlier on the same stream.
+template <bool kDict>
+__device__ __forceinline__
+void frame_index_body(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
+                      const uint32_t* __restrict__ crc, uint32_t n_blocks, uint64_t content_bytes,
+                      uint32_t win_bits, uint32_t block_bits, uint8_t* __restrict__ frame, uint64_t capacity,
+                      uint64_t* __restrict__ copy_bytes, uint64_t* __restrict__ dense_off,
+                      uint64_t* __restrict__ idx_off, uint64_t* __restrict__ frame_bytes_out,
+                      int32_t* __restrict__ status_out, uint32_t flags, uint32_t* __restrict__ stored,
+                      uint32_t dict_bytes, const uint32_t* __restrict__ dict_crc) {
     __shared__ uint64_t sums[256];
     __shared__ int32_t first_err[256];
     __shared__ int32_t verdict;
@@ -285,7 +293,8 @@ void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* _
     const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
     const bool store = (flags & kFrameStored) != 0;
     const uint64_t bb = 1ull << block_bits;
-    const uint64_t most_words = store ? 0x7FFFFFFFull : 0xFFFFFFFFull;     // bit 31 of the entry is the stored bit
+    const uint64_t most_words = store || kDict ? 0x7FFFFFFFull : 0xFFFFFFFFull;    // bit 31 of the entry is the stored bit
+    const uint64_t record = kDict ? 8 : 0;
     uint64_t sum = 0;
     int32_t bad = 0;
     for (uint64_t b = b0; b < b1; b++) {
@@ -297,7 +306,7 @@ void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* _
     sums[t] = sum;
     first_err[t] = bad;
     __syncthreads();
-    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + 15) & ~(uint64_t)15;
+    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + record + 15) & ~(uint64_t)15;
     if (t == 0) {
         uint64_t run = 0;
         int32_t st = 0;
@@ -313,17 +322,21 @@ void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* _
         *frame_bytes_out = frame_bytes;
         *status_out = st;
         idx_off[0] = st == 0 ? 32 : 0;
-        idx_off[1] = st == 0 ? 32 + 8 * (uint64_t)n_blocks : 0;
+        idx_off[1] = st == 0 ? 32 + 8 * (uint64_t)n_blocks + record : 0;
         if (st == 0) {
             uint32_t* const h = reinterpret_cast<uint32_t*>(frame);
             h[0] = 0x465A5153u;                                    // "SQZF"
-            h[1] = (store ? 2u : 1u) | (win_bits << 8) | (block_bits << 16) | ((flags & 0xFFu) << 24);     // version,
-                                                                   // win_bits, block_bits, flags
+            h[1] = (kDict ? 3u : store ? 2u : 1u) | (win_bits << 8) | (block_bits << 16) | ((flags & 0xFFu) << 24);
+                                                                   // version, win_bits, block_bits, flags
             h[2] = (uint32_t)content_bytes; h[3] = (uint32_t)(content_bytes >> 32);
             h[4] = (uint32_t)run; h[5] = (uint32_t)(run >> 32);
             h[6] = n_blocks;
             h[7] = 0u;                                             // index_crc: frame_seal_kernel
-            if ((n_blocks & 1u) != 0) { h[8 + 2 * (uint64_t)n_blocks] = 0u; h[9 + 2 * (uint64_t)n_blocks] = 0u; }
+            uint32_t* const behind = h + 8 + 2 * (uint64_t)n_blocks;       // what follows the n entries
+            if (kDict) {
+                behind[0] = dict_bytes; behind[1] = *dict_crc;
+                if ((n_blocks & 1u) == 0) { behind[2] = 0u; behind[3] = 0u; }
+            } else if ((n_blocks & 1u) != 0) { behind[0] = 0u; behind[1] = 0u; }
         }
     }
     __syncthreads();
@@ -344,6 +357,30 @@ void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* _
     if (b1 == n_blocks && (b0 < b1 || t == 0)) { dense_off[n_blocks] = ok ? at : 0; }
 }
 
+__global__ __launch_bounds__(256)
+void frame_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
+                        const uint32_t* __restrict__ crc, uint32_t n_blocks, uint64_t content_bytes,
+                        uint32_t win_bits, uint32_t block_bits, uint8_t* __restrict__ frame, uint64_t capacity,
+                        uint64_t* __restrict__ copy_bytes, uint64_t* __restrict__ dense_off,
+                        uint64_t* __restrict__ idx_off, uint64_t* __restrict__ frame_bytes_out,
+                        int32_t* __restrict__ status_out, uint32_t flags, uint32_t* __restrict__ stored) {
+    frame_index_body<false>(out_bytes, err, crc, n_blocks, content_bytes, win_bits, block_bits, frame, capacity,
+                            copy_bytes, dense_off, idx_off, frame_bytes_out, status_out, flags, stored, 0u, nullptr);
+}
+
+__global__ __launch_bounds__(256)
+void frame_index_v3_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
+                           const uint32_t* __restrict__ crc, uint32_t n_blocks, uint64_t content_bytes,
+                           uint32_t win_bits, uint32_t block_bits, uint8_t* __restrict__ frame, uint64_t capacity,
+                           uint64_t* __restrict__ copy_bytes, uint64_t* __restrict__ dense_off,
+                           uint64_t* __restrict__ idx_off, uint64_t* __restrict__ frame_bytes_out,
+                           int32_t* __restrict__ status_out, uint32_t flags, uint32_t* __restrict__ stored,
+                           uint32_t dict_bytes, const uint32_t* __restrict__ dict_crc) {
+    frame_index_body<true>(out_bytes, err, crc, n_blocks, content_bytes, win_bits, block_bits, frame, capacity,
+                           copy_bytes, dense_off, idx_off, frame_bytes_out, status_out, flags, stored, dict_bytes,
+                           dict_crc);
+}
+
 void launch_frame_index(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
                         uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint8_t* frame,
                         uint64_t capacity, uint64_t* copy_bytes, uint64_t* dense_off, uint64_t* idx_off,
@@ -362,21 +399,33 @@ void launch_frame_index_v2(const uint64_t* out_bytes, const int32_t* err, const 
                        frame_bytes_out, status_out, kFrameStored, stored);
 }
 
+void launch_frame_index_v3(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
+                           uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint32_t flags,
+                           uint32_t dict_bytes, const uint32_t* dict_crc, uint8_t* frame, uint64_t capacity,
+                           uint64_t* copy_bytes, uint64_t* dense_off, uint32_t* stored, uint64_t* idx_off,
+                           uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_index_v3_kernel, dim3(1), dim3(256), 0, stream, out_bytes, err, crc, n_blocks,
+                       content_bytes, win_bits, block_bits, frame, capacity, copy_bytes, dense_off, idx_off,
+                       frame_bytes_out, status_out, (flags & kFrameStored) | kFrameDict, stored, dict_bytes, dict_crc);
+}
+
 // index_crc = crc32(header[0, 28) || index): the header's 28 bytes on the spot, joined with the index's
-// checksum (idx_crc, from crc32_blocks_kernel) by crc(A || B) = crc(A) * x^(8|B|) ^ crc(B)
+// checksum (idx_crc, from crc32_blocks_kernel) by crc(A || B) = crc(A) * x^(8|B|) ^ crc(B).  idx_bytes: what
+// idx_crc covers, 8 n_blocks, and 8 more in a version-3 frame (the dictionary's record)
 __global__ __launch_bounds__(64)
-void frame_seal_kernel(uint8_t* __restrict__ frame, const uint32_t* __restrict__ idx_crc, uint32_t n_blocks,
+void frame_seal_kernel(uint8_t* __restrict__ frame, const uint32_t* __restrict__ idx_crc, uint64_t idx_bytes,
                        const int32_t* __restrict__ status) {
     const int lane = (int)threadIdx.x;
     if (*status != 0) { return; }
     const uint32_t h = crc32_small(frame, 28);
-    const uint32_t c = gf_mul(h, xpow8_wave(8 * (uint64_t)n_blocks, lane)) ^ *idx_crc;
+    const uint32_t c = gf_mul(h, xpow8_wave(idx_bytes, lane)) ^ *idx_crc;
     if (lane == 0) { reinterpret_cast<uint32_t*>(frame)[7] = c; }
 }
 
 void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_blocks, const int32_t* status,
-                       hipStream_t stream) {
-    hipLaunchKernelGGL(frame_seal_kernel, dim3(1), dim3(64), 0, stream, frame, idx_crc, n_blocks, status);
+                       hipStream_t stream, uint32_t record_bytes) {
+    hipLaunchKernelGGL(frame_seal_kernel, dim3(1), dim3(64), 0, stream, frame, idx_crc,
+                       8 * (uint64_t)n_blocks + record_bytes, status);
 }
 
 // ---------------------------------------------------------------------------------------- decode side
@@ -391,12 +440,24 @@ void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_block
 // entry's first word marks a stored block, the other 31 bits are its share of the payload in words, which for a
 // stored block must be ceil(length / 8) exactly (EINVAL, checked once index_crc has held).  stored[k] = 1 for a
 // selected stored block, 0 otherwise -- all zeros for a version-1 frame and on any refusal.
-__global__ __launch_bounds__(256)
-void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
-                       uint64_t content_bytes, uint32_t first, uint32_t n_sel,
-                       const uint32_t* __restrict__ idx_crc, uint64_t* __restrict__ in_off,
-                       uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out,
-                       uint32_t* __restrict__ stored) {
+//
+// kDict is the reader of version 3, and of nothing else (versions 1 and 2 are EINVAL through it, as version 3 is
+// through the other).  idx_crc then covers frame[32, 32 + 8 n + 8), the index and the record; dict_bytes and
+// *dict_crc describe the dictionary the caller brought (crc32_blocks_kernel over it, earlier on the stream).  The
+// checks in the host's order (sqz_frame_info, then its dictionary check): header fields EINVAL, header against the
+// arguments EINVAL, index_crc EILSEQ, the record's dict_bytes outside 1 .. window - 1 EINVAL, a stored entry without
+// flags bit 0 or of the wrong size EINVAL, the words' sum EINVAL, a record that is not (dict_bytes, *dict_crc)
+// EILSEQ, the payload beyond avail E2BIG.
+// want_bits (either flavour): the block_bits the caller's own arithmetic used, 0 when it used none; a frame with
+// another is EINVAL with the header's other disagreements (a ranged read works first and n_sel out on the host).
+template <bool kDict>
+__device__ __forceinline__
+void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
+                     uint64_t content_bytes, uint32_t first, uint32_t n_sel,
+                     const uint32_t* __restrict__ idx_crc, uint64_t* __restrict__ in_off,
+                     uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out,
+                     uint32_t* __restrict__ stored, uint32_t dict_bytes, const uint32_t* __restrict__ dict_crc,
+                     uint32_t want_bits) {
     __shared__ uint64_t sums[256];
     __shared__ uint32_t wrong[256];
     __shared__ int32_t verdict;
@@ -405,7 +466,7 @@ void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32
     const int lane = (int)(t & 63u);
     if (t < 64) {                                  // wave 0, all of it: what index_crc has to be
         const uint32_t h = crc32_small(frame, 28);
-        const uint32_t c = gf_mul(h, xpow8_wave(8 * (uint64_t)n_blocks, lane)) ^ *idx_crc;
+        const uint32_t c = gf_mul(h, xpow8_wave(8 * (uint64_t)n_blocks + (kDict ? 8 : 0), lane)) ^ *idx_crc;
         if (lane == 0) { want_crc = c; }
     }
     const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
@@ -413,20 +474,22 @@ void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32
     const uint64_t b0 = t * per < n_blocks ? t * per : n_blocks;
     const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
     const uint32_t block_bits = frame[6];
-    const bool v2 = frame[4] == 2;
+    const bool v2 = kDict ? frame[4] == 3 : frame[4] == 2;         // an entry's bit 31 is the stored bit
+    const bool may_store = !kDict || (frame[7] & kFrameStored) != 0;       // version 3 has the bit with or without the flag
     const uint32_t words_mask = v2 ? ~kStoredBit : 0xFFFFFFFFu;
     uint64_t sum = 0;
-    uint32_t misfit = 0;                           // a stored entry whose size is not its block's
+    uint32_t misfit = 0;                           // a stored entry whose size is not its block's, or in a frame without any
     for (uint64_t b = b0; b < b1; b++) {
         const uint32_t e = index[2 * b];
         if (v2 && (e & kStoredBit) != 0 && block_bits <= 24 &&
-            (uint64_t)(e & words_mask) != (block_len(b, 1ull << block_bits, content_bytes) + 7) / 8) { misfit = 1; }
+            (!may_store ||
+             (uint64_t)(e & words_mask) != (block_len(b, 1ull << block_bits, content_bytes) + 7) / 8)) { misfit = 1; }
         sum += (uint64_t)(e & words_mask) * 8;
     }
     sums[t] = sum;
     wrong[t] = misfit;
     __syncthreads();
-    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + 15) & ~(uint64_t)15;
+    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + (kDict ? 8 : 0) + 15) & ~(uint64_t)15;
     if (t == 0) {
         uint64_t run = 0;
         bool beyond = false;                       // the streams add up to more than there is: stop adding (no wrap)
@@ -439,9 +502,13 @@ void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32
         }
         int32_t st = 0;
         const uint32_t win_bits = frame[5];
-        // version 1 has no flags; version 2 has some, all of them known, and needs somewhere to put the mask
-        const bool version_ok = (frame[4] == 1 && frame[7] == 0) ||
-                                (frame[4] == 2 && frame[7] == kFrameStored && (stored != nullptr || n_sel == 0));
+        // version 1 has no flags; version 2 has some, all of them known, and needs somewhere to put the mask;
+        // version 3 has bit 1, perhaps bit 0, no other, and needs the mask as well
+        const bool version_ok = kDict ? frame[4] == 3 && (frame[7] & kFrameDict) != 0 &&
+                                        (frame[7] & ~(kFrameStored | kFrameDict)) == 0 && (stored != nullptr || n_sel == 0)
+                                      : (frame[4] == 1 && frame[7] == 0) ||
+                                        (frame[4] == 2 && frame[7] == kFrameStored && (stored != nullptr || n_sel == 0));
+        const uint8_t* const rec = frame + 32 + 8 * (uint64_t)n_blocks;    // (version 3: the caller saw to avail)
         if (load_le32(frame) != 0x465A5153u || !version_ok || win_bits < 10 || win_bits > 15 ||
             block_bits < 12 || block_bits > 24) {
             st = kErrEINVAL;
@@ -449,14 +516,18 @@ void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32
             const uint64_t bb = 1ull << block_bits;
             const uint64_t want_n = content_bytes / bb + ((content_bytes & (bb - 1)) != 0 ? 1 : 0);
             if (load_le64(frame + 8) != content_bytes || load_le32(frame + 24) != n_blocks || want_n != n_blocks ||
-                (uint64_t)first + n_sel > n_blocks) {
+                (uint64_t)first + n_sel > n_blocks || (want_bits != 0 && block_bits != want_bits)) {
                 st = kErrEINVAL;
             } else if (load_le32(frame + 28) != want_crc) {
                 st = kErrEILSEQ;
+            } else if (kDict && (load_le32(rec) == 0 || load_le32(rec) > (1u << win_bits) - 1u)) {
+                st = kErrEINVAL;
             } else if (any_misfit != 0) {
                 st = kErrEINVAL;
             } else if (!beyond && load_le64(frame + 16) != run) {
                 st = kErrEINVAL;
+            } else if (kDict && (load_le32(rec) != dict_bytes || load_le32(rec + 4) != *dict_crc)) {
+                st = kErrEILSEQ;
             } else if (beyond || payload_off > avail || run > avail - payload_off) {
                 st = kErrE2BIG;
             }
@@ -490,18 +561,48 @@ void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32
     }
 }
 
+__global__ __launch_bounds__(256)
+void frame_open_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
+                       uint64_t content_bytes, uint32_t first, uint32_t n_sel,
+                       const uint32_t* __restrict__ idx_crc, uint64_t* __restrict__ in_off,
+                       uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out,
+                       uint32_t* __restrict__ stored, uint32_t want_bits) {
+    frame_open_body<false>(frame, avail, n_blocks, content_bytes, first, n_sel, idx_crc, in_off, out_off, status_out,
+                           stored, 0u, nullptr, want_bits);
+}
+
+__global__ __launch_bounds__(256)
+void frame_open_v3_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
+                          uint64_t content_bytes, uint32_t first, uint32_t n_sel,
+                          const uint32_t* __restrict__ idx_crc, uint64_t* __restrict__ in_off,
+                          uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out,
+                          uint32_t* __restrict__ stored, uint32_t dict_bytes, const uint32_t* __restrict__ dict_crc,
+                          uint32_t want_bits) {
+    frame_open_body<true>(frame, avail, n_blocks, content_bytes, first, n_sel, idx_crc, in_off, out_off, status_out,
+                          stored, dict_bytes, dict_crc, want_bits);
+}
+
 void launch_frame_open(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
                        uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
                        uint64_t* out_off, int32_t* status_out, hipStream_t stream) {
     hipLaunchKernelGGL(frame_open_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
-                       first, n_sel, idx_crc, in_off, out_off, status_out, (uint32_t*)nullptr);
+                       first, n_sel, idx_crc, in_off, out_off, status_out, (uint32_t*)nullptr, 0u);
 }
 
 void launch_frame_open_v2(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
                           uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
-                          uint64_t* out_off, uint32_t* stored, int32_t* status_out, hipStream_t stream) {
+                          uint64_t* out_off, uint32_t* stored, int32_t* status_out, hipStream_t stream,
+                          uint32_t want_bits) {
     hipLaunchKernelGGL(frame_open_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
-                       first, n_sel, idx_crc, in_off, out_off, status_out, stored);
+                       first, n_sel, idx_crc, in_off, out_off, status_out, stored, want_bits);
+}
+
+void launch_frame_open_v3(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                          uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint32_t dict_bytes,
+                          const uint32_t* dict_crc, uint64_t* in_off, uint64_t* out_off, uint32_t* stored,
+                          int32_t* status_out, hipStream_t stream, uint32_t want_bits) {
+    hipLaunchKernelGGL(frame_open_v3_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
+                       first, n_sel, idx_crc, in_off, out_off, status_out, stored, dict_bytes, dict_crc, want_bits);
 }
 
 // err[k] for the selected blocks: the frame's status where it was refused; EILSEQ where the decoder was
@@ -523,6 +624,38 @@ void launch_frame_verify(const uint8_t* frame, uint32_t first, uint32_t n_sel, c
     if (n_sel == 0) { return; }
     hipLaunchKernelGGL(frame_verify_kernel, dim3((n_sel + 255) / 256), dim3(256), 0, stream,
                        frame, first, n_sel, crc, status, err);
+}
+
+// A ranged read from a resident frame, once the covering blocks [first, first + n_sel) lie decoded and verified in
+// scratch: *status = the frame's status, otherwise the first non-zero err[k]; and a one-range work list for
+// range_copy_kernel -- `length` bytes from `src_at` (the range's place in the decoded blocks) to the start of the
+// caller's buffer, masked out unless everything held, so that the copy moves the range or nothing.
+// plan: src_off = plan[0], dst_off = len_off = plan + 2 ({0, length}), mask = (uint32_t*)(plan + 4).
+__global__ __launch_bounds__(256)
+void frame_read_plan_kernel(const int32_t* __restrict__ err, uint32_t n_sel, uint64_t src_at, uint64_t length,
+                            uint64_t* __restrict__ plan, int32_t* __restrict__ status) {
+    __shared__ uint32_t first_bad[256];
+    const uint32_t t = threadIdx.x;
+    uint32_t mine = 0xFFFFFFFFu;                   // the first block of this lane's that failed
+    for (uint64_t k = t; k < n_sel; k += 256) {
+        if (err[k] != 0) { mine = (uint32_t)k; break; }
+    }
+    first_bad[t] = mine;
+    __syncthreads();
+    if (t != 0) { return; }
+    uint32_t bad = 0xFFFFFFFFu;
+    for (int k = 0; k < 256; k++) { bad = first_bad[k] < bad ? first_bad[k] : bad; }
+    int32_t st = *status;
+    if (st == 0 && bad != 0xFFFFFFFFu) { st = err[bad]; }
+    *status = st;
+    plan[0] = src_at;
+    plan[2] = 0; plan[3] = length;
+    *reinterpret_cast<uint32_t*>(plan + 4) = st == 0 ? 1u : 0u;
+}
+
+void launch_frame_read_plan(const int32_t* err, uint32_t n_sel, uint64_t src_at, uint64_t length, uint64_t* plan,
+                            int32_t* status, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_read_plan_kernel, dim3(1), dim3(256), 0, stream, err, n_sel, src_at, length, plan, status);
 }
 
 // ---------------------------------------------------------------------------------------- stored blocks

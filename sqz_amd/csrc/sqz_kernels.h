@@ -98,8 +98,9 @@ void launch_frame_index(const uint64_t* out_bytes, const int32_t* err, const uin
                         uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint8_t* frame,
                         uint64_t capacity, uint64_t* copy_bytes, uint64_t* dense_off, uint64_t* idx_off,
                         uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream);
+// (record_bytes: 8 for a version-3 frame, whose index checksum covers the dictionary's record as well)
 void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_blocks, const int32_t* status,
-                       hipStream_t stream);
+                       hipStream_t stream, uint32_t record_bytes = 0);
 // decode: header and index checks, offsets of blocks [first, first + n_sel) for the decode kernels
 void launch_frame_open(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
                        uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
@@ -113,13 +114,35 @@ void launch_frame_index_v2(const uint64_t* out_bytes, const int32_t* err, const 
                            uint64_t* idx_off, uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream);
 void launch_frame_open_v2(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
                           uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
-                          uint64_t* out_off, uint32_t* stored, int32_t* status_out, hipStream_t stream);
+                          uint64_t* out_off, uint32_t* stored, int32_t* status_out, hipStream_t stream,
+                          uint32_t want_bits = 0);
 // ragged copy: len_off[b+1] - len_off[b] bytes from src + src_off[b] to dst + dst_off[b] where mask[b] != 0
 // (null: everywhere), any alignment; pad8: zeros up to the next multiple of 8 behind each range.  size_hint
 // as for launch_crc32_blocks
 void launch_range_copy(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, const uint64_t* dst_off,
                        const uint64_t* len_off, const uint32_t* mask, uint32_t n_ranges, bool pad8,
                        uint64_t size_hint, hipStream_t stream);
+// version 3 (SQZ_FRAME_DICT, with or without SQZ_FRAME_STORED in `flags`): kernels of their own over the same code.
+// index: the record { dict_bytes, *dict_crc } behind the entries, idx_off = {32, 32 + 8n + 8}; launch_frame_seal then
+// takes record_bytes = 8.  open: idx_crc covers frame[32, 32 + 8n + 8); only a version-3 frame whose record is
+// (dict_bytes, *dict_crc) passes (EILSEQ otherwise; EINVAL for versions 1 and 2).  dict_crc: a device pointer to the
+// CRC-32 of the caller's dictionary, written by launch_crc32_blocks earlier on the stream.  stored: as for _v2,
+// needed for n_sel > 0 (index: only with SQZ_FRAME_STORED).  want_bits (open, _v2 as well): when not 0, a frame
+// whose block_bits is another is EINVAL -- for a caller that worked `first` and `n_sel` out from a block_bits
+void launch_frame_index_v3(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
+                           uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint32_t flags,
+                           uint32_t dict_bytes, const uint32_t* dict_crc, uint8_t* frame, uint64_t capacity,
+                           uint64_t* copy_bytes, uint64_t* dense_off, uint32_t* stored, uint64_t* idx_off,
+                           uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream);
+void launch_frame_open_v3(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                          uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint32_t dict_bytes,
+                          const uint32_t* dict_crc, uint64_t* in_off, uint64_t* out_off, uint32_t* stored,
+                          int32_t* status_out, hipStream_t stream, uint32_t want_bits = 0);
+// a ranged read's last step but one: *status = the frame's status, else the first non-zero err[0 .. n_sel); and the
+// one-range work list of launch_range_copy(src, plan, dst, plan + 2, plan + 2, (uint32_t*)(plan + 4), 1, ..):
+// `length` bytes from src + src_at to dst, masked out unless *status == 0.  plan: 5 x uint64
+void launch_frame_read_plan(const int32_t* err, uint32_t n_sel, uint64_t src_at, uint64_t length, uint64_t* plan,
+                            int32_t* status, hipStream_t stream);
 void launch_frame_verify(const uint8_t* frame, uint32_t first, uint32_t n_sel, const uint32_t* crc,
                          const int32_t* status, int32_t* err, hipStream_t stream);
 

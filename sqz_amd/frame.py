@@ -20,7 +20,7 @@ import ctypes as C
 import errno
 
 from . import _native as N
-from .codec import PARSE_LAZY, SqzError, _raise, dict_bytes, parse_code
+from .codec import MAX_DICT_BYTES, PARSE_LAZY, SqzError, _raise, dict_bytes, parse_code
 
 HEADER_BYTES = 32
 FRAME_STORED = 1            # SQZ_FRAME_STORED
@@ -167,30 +167,63 @@ def crc32_blocks(d_in, in_off, crc=None):
     return crc[:n]
 
 
+def _dict_dev(dictionary, window, device):
+    """A shared dictionary on the device, its length checked before anything native is called: bytes-like, or a
+    uint8 tensor that is there already (used as it is: the caller keeps it alive until the stream has passed).
+    A tensor made here comes from torch's allocator on the current stream, which does not hand its memory to
+    another stream while work enqueued on this one may still read it."""
+    import torch
+    if isinstance(dictionary, torch.Tensor):
+        if dictionary.dtype != torch.uint8 or dictionary.dim() != 1:
+            raise ValueError("dictionary tensor must be one-dimensional uint8")
+        most = MAX_DICT_BYTES if window is None else min(window - 1, MAX_DICT_BYTES)
+        if not 1 <= dictionary.numel() <= most:
+            raise ValueError(f"dictionary must be 1 .. {most} bytes, not {dictionary.numel()}")
+        return dictionary.contiguous().to(device)
+    d = dict_bytes(dictionary, window)
+    return torch.frombuffer(bytearray(d), dtype=torch.uint8).to(device)
+
+
 class FrameEncoder:
     """Reusable device buffers for frames of up to `content_bytes` bytes at (win_bits, block_bits).
-    encode() enqueues and returns; frame_bytes / status / err are device tensors to read after a synchronise."""
+    encode() enqueues and returns; frame_bytes / status / err are device tensors to read after a synchronise.
+    dictionary (bytes-like or a uint8 device tensor of 1 .. window - 1 bytes): version-3 frames, byte for byte
+    compress_frame(..., dictionary=)'s; it is kept on the device for the encoder's life."""
 
     def __init__(self, content_bytes: int, win_bits: int = 15, block_bits: int = 18, capacity: int = None,
-                 device="cuda", store: bool = False, parse: str = "greedy"):
+                 device="cuda", store: bool = False, parse: str = "greedy", dictionary=None):
         import torch
         self.parse = parse_code(parse)
         L = N.lib()
         self.win_bits, self.block_bits, self.content_bytes = win_bits, block_bits, content_bytes
         self.flags = _flags(store)
-        self.capacity = frame_bound(content_bytes, block_bits, store) if capacity is None else capacity
+        self.dictionary = _dict_dev(dictionary, 1 << win_bits, device) if dictionary is not None else None
+        if capacity is None:
+            capacity = frame_bound(content_bytes, block_bits, store, self.dictionary is not None)
+        self.capacity = capacity
         self.n_blocks = (content_bytes + (1 << block_bits) - 1) >> block_bits
         self.frame = torch.empty(max(self.capacity, 16), dtype=torch.uint8, device=device)
         self.frame_bytes = torch.zeros(1, dtype=torch.int64, device=device)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
         self.err = torch.zeros(max(self.n_blocks, 1), dtype=torch.int32, device=device)
-        self.scratch_bytes = int(L.sqz_hip_frame_scratch_bytes_ex(content_bytes, block_bits, 1, self.flags))
+        if self.dictionary is not None:
+            self.scratch_bytes = int(L.sqz_hip_frame_scratch_bytes_dict(content_bytes, block_bits, 1, self.flags,
+                                                                        self.dictionary.numel()))
+        else:
+            self.scratch_bytes = int(L.sqz_hip_frame_scratch_bytes_ex(content_bytes, block_bits, 1, self.flags))
         self.scratch = torch.empty(self.scratch_bytes, dtype=torch.uint8, device=device)
 
     def encode(self, d_in, content_bytes: int = None):
         nbytes = d_in.numel() if content_bytes is None else content_bytes
         if nbytes > self.content_bytes:
             raise SqzError(errno.E2BIG, "FrameEncoder: more content than the buffers were made for")
+        if self.dictionary is not None:
+            _raise(N.lib().sqz_hip_frame_encode_dict(
+                _ptr(d_in), nbytes, self.win_bits, self.block_bits, self.flags | FRAME_DICT, self.parse,
+                _ptr(self.dictionary), self.dictionary.numel(), _ptr(self.frame), self.capacity,
+                _ptr(self.frame_bytes), _ptr(self.status), _ptr(self.err), _ptr(self.scratch), self.scratch_bytes,
+                _stream()), "sqz_hip_frame_encode_dict")
+            return self.frame, self.frame_bytes, self.status, self.err
         if self.parse == PARSE_LAZY:
             _raise(N.lib().sqz_hip_frame_encode_parse(
                 _ptr(d_in), nbytes, self.win_bits, self.block_bits, self.flags, self.parse, _ptr(self.frame),
@@ -214,9 +247,22 @@ class FrameEncoder:
 _decode_scratch = {}
 
 
-def decode_frame(d_frame, d_out, info: dict = None, err=None, status=None, scratch=None):
+def _scratch_for(device, need: int):
+    key = str(device)
+    scratch = _decode_scratch.get(key)
+    if scratch is None or scratch.numel() < need:
+        import torch
+        scratch = torch.empty(need, dtype=torch.uint8, device=device)
+        _decode_scratch[key] = scratch
+    return scratch
+
+
+def decode_frame(d_frame, d_out, info: dict = None, err=None, status=None, scratch=None, dictionary=None):
     """A device-resident frame into the caller's uint8 tensor.  `info` = frame_info() of the header (fetched
-    with one 32-byte copy when not given).  Enqueues and returns (err int32[n_blocks], status int32[1])."""
+    with one 32-byte copy when not given).  Enqueues and returns (err int32[n_blocks], status int32[1]).
+    dictionary (bytes-like or a uint8 device tensor): what a version-3 frame was written with; a wrong one is status
+    EILSEQ with nothing written, a frame of version 1 or 2 with one EINVAL.  Without one the call knows versions 1
+    and 2 and refuses a version-3 frame (status EINVAL)."""
     import torch
     L = N.lib()
     if info is None:
@@ -224,20 +270,61 @@ def decode_frame(d_frame, d_out, info: dict = None, err=None, status=None, scrat
     n, content = info["n_blocks"], info["content_bytes"]
     if d_out.numel() < content:
         raise SqzError(errno.E2BIG, "decode_frame: d_out is smaller than the content")
+    d = _dict_dev(dictionary, 1 << info["win_bits"], d_out.device) if dictionary is not None else None
     if err is None:
         err = torch.zeros(max(n, 1), dtype=torch.int32, device=d_out.device)
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=d_out.device)
+    if d is not None:
+        if scratch is None:
+            scratch = _scratch_for(d_out.device, int(L.sqz_hip_frame_scratch_bytes_dict(
+                content, info["block_bytes"].bit_length() - 1, 0, FRAME_DICT, d.numel())))
+        _raise(L.sqz_hip_frame_decode_dict(_ptr(d_frame), d_frame.numel(), n, content, _ptr(d), d.numel(), _ptr(d_out),
+                                           _ptr(err), _ptr(status), _ptr(scratch), scratch.numel(), _stream()),
+               "sqz_hip_frame_decode_dict")
+        return err[:n], status
     need = int(L.sqz_hip_frame_scratch_bytes(content, info["block_bytes"].bit_length() - 1, 0))
     if scratch is None:
-        key = str(d_out.device)
-        scratch = _decode_scratch.get(key)
-        if scratch is None or scratch.numel() < need:
-            scratch = torch.empty(need, dtype=torch.uint8, device=d_out.device)
-            _decode_scratch[key] = scratch
+        scratch = _scratch_for(d_out.device, need)
     _raise(L.sqz_hip_frame_decode(_ptr(d_frame), d_frame.numel(), n, content, _ptr(d_out), _ptr(err), _ptr(status),
                                   _ptr(scratch), scratch.numel(), _stream()), "sqz_hip_frame_decode")
     return err[:n], status
+
+
+def read_frame(d_frame, offset: int, length: int, d_out=None, info: dict = None, dictionary=None, err=None,
+               status=None, scratch=None):
+    """content[offset : offset + length] of a device-resident frame into d_out (uint8, made when not given): only
+    the covering blocks are decoded, into the scratch, and verified.  `info` as for decode_frame; dictionary: as
+    for decode_frame, needed for a version-3 frame.  Enqueues and returns (d_out[:length], err int32[covering
+    blocks], status int32[1]): d_out holds the range when status is 0 after a synchronise and is untouched
+    otherwise.  A range that leaves the content raises EINVAL here."""
+    import torch
+    L = N.lib()
+    if info is None:
+        info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    n, content, bits = info["n_blocks"], info["content_bytes"], info["block_bytes"].bit_length() - 1
+    device = d_frame.device
+    d = _dict_dev(dictionary, 1 << info["win_bits"], device) if dictionary is not None else None
+    if d_out is None:
+        d_out = torch.empty(max(length, 1), dtype=torch.uint8, device=device)
+    elif d_out.numel() < length:
+        raise SqzError(errno.E2BIG, "read_frame: d_out is smaller than the range")
+    covering = ((offset + length - 1) >> bits) - (offset >> bits) + 1 if length > 0 else 0
+    if err is None:
+        err = torch.zeros(max(covering, 1), dtype=torch.int32, device=device)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=device)
+    if scratch is None:
+        scratch = _scratch_for(device, int(L.sqz_hip_frame_read_scratch_bytes(length, bits)))
+    if d is not None:
+        _raise(L.sqz_hip_frame_read_dict(_ptr(d_frame), d_frame.numel(), n, content, bits, offset, length, _ptr(d),
+                                         d.numel(), _ptr(d_out), _ptr(err), _ptr(status), _ptr(scratch),
+                                         scratch.numel(), _stream()), "sqz_hip_frame_read_dict")
+    else:
+        _raise(L.sqz_hip_frame_read(_ptr(d_frame), d_frame.numel(), n, content, bits, offset, length, _ptr(d_out),
+                                    _ptr(err), _ptr(status), _ptr(scratch), scratch.numel(), _stream()),
+               "sqz_hip_frame_read")
+    return d_out[:length], err[:covering], status
 
 
 # ---- file tool ----------------------------------------------------------------------------------
