@@ -637,6 +637,58 @@ SQZ_API int sqz_hip_frame_read_dict(const void* d_frame, uint64_t avail, uint32_
                                     uint64_t dict_bytes, void* d_out, int32_t* d_err, int32_t* d_status,
                                     void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* Many byte ranges of a resident frame in one call.  As sqz_hip_frame_read / _read_dict (device pointers, d_frame and
+ * d_scratch 16-byte aligned, asynchronous, no host synchronisation inside; n_blocks, content_bytes and block_bits from
+ * a host copy of the header), but d_offset and d_length, n_ranges values each, lie in DEVICE memory and are never read
+ * by the host.  The host knows n_ranges, max_length -- a hard cap on every range's length -- and max_blocks, a cap on
+ * the number of DISTINCT covering blocks (anything up to n_blocks; more counts as n_blocks;
+ * min(n_blocks, n_ranges * (((max_length + 2^b - 2) >> b) + 1)) is always enough).
+ *
+ * Range r is valid iff length[r] <= max_length, offset[r] <= content_bytes and length[r] <= content_bytes - offset[r]
+ * (no wrap of offset + length).  An invalid range gets d_range_err[r] = EINVAL, counts as length 0 and covers
+ * nothing; a valid range of length 0 is delivered (0) and covers nothing.  d_out_off (n_ranges + 1 entries) is the
+ * exclusive prefix sum of the valid ranges' lengths in request order: it depends on the ranges alone and is written
+ * even when the frame is refused.  Range r is delivered to d_out[d_out_off[r], d_out_off[r + 1]).
+ *
+ * *d_status: the frame's status -- the checks of sqz_hip_frame_decode / _decode_dict in their order, EINVAL also for a
+ *   frame whose block_bits is another, E2BIG unless the whole frame lies inside avail, EILSEQ for a wrong dictionary:
+ *   *d_status and every valid range's d_range_err get it, *d_blocks_decoded = 0, d_out is not written.
+ *   Otherwise ENOBUFS when the distinct covering blocks are more than max_blocks, else ENOSPC when
+ *   d_out_off[n_ranges] > out_capacity: nothing is decoded, d_out is not written, every valid range's d_range_err gets
+ *   the status, and *d_blocks_decoded still holds the distinct count, so the caller knows what to ask for.  Nothing is
+ *   ever written past either cap.
+ *   Otherwise 0: every distinct covering block is decoded ONCE into the scratch and verified against its CRC-32, and
+ *   *d_blocks_decoded is their number.  For a valid range d_range_err[r] is the first non-zero errno among its
+ *   covering blocks in ascending order (EILSEQ for a checksum that does not hold, otherwise the decoder's); a range
+ *   with a non-zero value is NOT written, the others are: a damaged block costs the ranges that touch it and nothing
+ *   else, and *d_status stays 0.
+ * EINVAL at the call, nothing enqueued: block_bits outside 12..24; n_blocks != ceil(content_bytes / 2^block_bits); a
+ *   null or misaligned d_frame / d_scratch; a null d_status, d_blocks_decoded or d_out_off; n_ranges > 0 with a null
+ *   d_offset, d_length or d_range_err; max_blocks > 0 with a null d_out; a scratch smaller than the function says;
+ *   _dict: d_dict == NULL or dict_bytes outside 1..32767.  E2BIG when avail does not cover header and index (and
+ *   record), ENODEV without a device.  n_ranges == 0 writes d_out_off[0] = 0, *d_blocks_decoded = 0 and the frame's
+ *   status and decodes nothing.
+ * Scratch, with m = min(max_blocks, n_blocks), w = ceil(n_blocks / 32), every term rounded up to 256:
+ *       sqz_hip_frame_gather_scratch_bytes(n_blocks, n_ranges, max_blocks, b) =
+ *           2 * (4 w + 4) + 256 + (4 m + 4) + 2 * 8 (2 m + 1) + 4 * (8 m + 4) + (8 n_ranges + 8) + (4 n_ranges + 4)
+ *           + sqz_hip_decode_scratch_bytes(2 m, m << b) + ((m << b) + 16)
+ *   (bitmap and its prefix counts, control words, the list, two offsets per slot, four masks and results per slot, the
+ *   copy's work list, the decoder's scratch, the decoded blocks); 0 for a bad block_bits.                            */
+SQZ_API uint64_t sqz_hip_frame_gather_scratch_bytes(uint32_t n_blocks, uint32_t n_ranges, uint32_t max_blocks,
+                                                    uint32_t block_bits);
+SQZ_API int sqz_hip_frame_gather(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                 uint32_t block_bits, const uint64_t* d_offset, const uint64_t* d_length,
+                                 uint32_t n_ranges, uint64_t max_length, uint32_t max_blocks, void* d_out,
+                                 uint64_t out_capacity, uint64_t* d_out_off, int32_t* d_range_err,
+                                 uint32_t* d_blocks_decoded, int32_t* d_status, void* d_scratch,
+                                 uint64_t scratch_bytes, void* stream);
+SQZ_API int sqz_hip_frame_gather_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                      uint32_t block_bits, const uint64_t* d_offset, const uint64_t* d_length,
+                                      uint32_t n_ranges, uint64_t max_length, uint32_t max_blocks, const void* d_dict,
+                                      uint64_t dict_bytes, void* d_out, uint64_t out_capacity, uint64_t* d_out_off,
+                                      int32_t* d_range_err, uint32_t* d_blocks_decoded, int32_t* d_status,
+                                      void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* Live timing of the last kernels enqueued through this library on the
  * calling thread's context, measured with HIP events ON THE LAUNCH STREAM.
  * Enabled with sqz_hip_set_timing(1); values in milliseconds.               */

@@ -21,6 +21,9 @@
 namespace {
 
 constexpr uint64_t kMaxStream = 1ull << 31;     // per-stream limit (32-bit freq/tokens)
+// a gather whose max_length is at most this copies with gather_copy_kernel (16 lanes per range), a longer one with
+// range_copy_kernel (a workgroup per range): DESIGN.md section 10, "Gather", has the measurement
+constexpr uint64_t sqzk_gather_copy_max = 4096;
 constexpr uint32_t sqzk_max_window = 1u << sqz_max_win_bits;   // a decode call has no window: the largest one bounds its dictionary
 
 // ---------------------------------------------------------------- device ctx
@@ -513,6 +516,7 @@ int decode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_o
 
 // ---------------------------------------------------------------- SQZF frames (include/sqz/sqz.h)
 static_assert(EINVAL == 22 && E2BIG == 7 && EILSEQ == 84, "frame.hip writes these errno values from the device");
+static_assert(ENOBUFS == 105 && ENOSPC == 28, "frame.hip writes these errno values from the device");
 
 uint32_t get_le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint64_t get_le64(const uint8_t* p) { return (uint64_t)get_le32(p) | ((uint64_t)get_le32(p + 4) << 32); }
@@ -676,10 +680,12 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
 // frame_open_kernel wrote, and the host decode of a version-3 frame, whose offsets the host worked out.
 void run_frame_decode(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* out_off, uint32_t n,
                       uint64_t size_hint, uint32_t* tokens, uint32_t* counts, uint8_t* d_out, int32_t* d_err,
-                      const uint32_t* skip, const uint32_t* stored, uint32_t* crc, const DictDev& dd, hipStream_t st) {
+                      const uint32_t* skip, const uint32_t* stored, uint32_t* crc, const DictDev& dd, hipStream_t st,
+                      uint32_t n_streams = 0) {
+    // n_streams: how many of the n entries can be streams at all, where that is fewer (a gather's pseudo-blocks)
     { SpanGuard g(st, SQZ_HIP_K_ENTROPY_DECODE);
-      sqzk::launch_entropy_decode(d_in, in_off, out_off, tokens, counts, d_err, nullptr, n, 0, decode_waves_for(n), st,
-                                  skip, dd.len); }
+      sqzk::launch_entropy_decode(d_in, in_off, out_off, tokens, counts, d_err, nullptr, n, 0,
+                                  decode_waves_for(n_streams != 0 ? n_streams : n), st, skip, dd.len); }
     { SpanGuard g(st, SQZ_HIP_K_LZ_EXPAND);
       sqzk::launch_lz_expand(tokens, counts, d_out, out_off, n, st, skip, dd.bytes, dd.len); }
     if (skip != nullptr) {                                  // a stored block ignores the dictionary
@@ -2076,6 +2082,146 @@ int sqz_hip_frame_read_dict(const void* d_frame, uint64_t avail, uint32_t n_bloc
     if (!dict_ok(d_dict, dict_bytes, (uint32_t)sqzk_max_window)) { return EINVAL; }
     return frame_read_call(d_frame, avail, n_blocks, content_bytes, block_bits, offset, length, d_dict, dict_bytes,
                            d_out, d_err, d_status, d_scratch, scratch_bytes, stream);
+}
+
+// ---- many ranges of a resident frame in one call
+// where the pieces of a gather's scratch lie (every piece 256-byte aligned); m = min(max_blocks, n_blocks) slots
+struct GatherScratch {
+    uint64_t bitmap, wpre, misc, sel, in_off, out_off, skip, stored, crc, err, src_off, mask, codec, codec_bytes, blocks, total;
+};
+static GatherScratch gather_scratch(uint64_t n, uint64_t r, uint64_t m, uint32_t block_bits) {
+    GatherScratch G = {};
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) { const uint64_t v = at; at += align_up(bytes, 256); return v; };
+    const uint64_t words = (n + 31) / 32;
+    G.bitmap = take(words * 4 + 4);
+    G.wpre = take(words * 4 + 4);
+    G.misc = take(256);                 // as a decode's, and [160,168) count and verdict of the select kernel
+    G.sel = take(m * 4 + 4);
+    G.in_off = take((2 * m + 1) * 8);   // two entries per slot: the block, and the gap behind its stream
+    G.out_off = take((2 * m + 1) * 8);
+    G.skip = take(2 * m * 4 + 4);
+    G.stored = take(2 * m * 4 + 4);
+    G.crc = take(2 * m * 4 + 4);
+    G.err = take(2 * m * 4 + 4);
+    G.src_off = take(r * 8 + 8);
+    G.mask = take(r * 4 + 4);
+    G.codec_bytes = sqz_hip_decode_scratch_bytes((uint32_t)(2 * m), m << block_bits);
+    G.codec = take(G.codec_bytes);
+    G.blocks = take((m << block_bits) + 16);
+    G.total = at;
+    return G;
+}
+
+uint64_t sqz_hip_frame_gather_scratch_bytes(uint32_t n_blocks, uint32_t n_ranges, uint32_t max_blocks, uint32_t block_bits) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits) { return 0; }
+    return gather_scratch(n_blocks, n_ranges, max_blocks < n_blocks ? max_blocks : n_blocks, block_bits).total;
+}
+
+// dict == NULL: versions 1 and 2 (sqz_hip_frame_gather); else version 3
+static int frame_gather_call(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                             uint32_t block_bits, const uint64_t* d_offset, const uint64_t* d_length, uint32_t n_ranges,
+                             uint64_t max_length, uint32_t max_blocks, const void* d_dict, uint64_t dict_bytes,
+                             void* d_out, uint64_t out_capacity, uint64_t* d_out_off, int32_t* d_range_err,
+                             uint32_t* d_blocks_decoded, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                             void* stream) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        frame_blocks(content_bytes, block_bits) != n_blocks) { return EINVAL; }
+    if (d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 || d_scratch == NULL || ((uintptr_t)d_scratch & 15u) != 0 ||
+        d_status == NULL || d_blocks_decoded == NULL || d_out_off == NULL ||
+        (n_ranges > 0 && (d_offset == NULL || d_length == NULL || d_range_err == NULL)) ||
+        (max_blocks > 0 && d_out == NULL)) { return EINVAL; }
+    const uint32_t m = max_blocks < n_blocks ? max_blocks : n_blocks;
+    const GatherScratch G = gather_scratch(n_blocks, n_ranges, m, block_bits);
+    if (scratch_bytes < G.total) { return EINVAL; }
+    const uint64_t record = d_dict != NULL ? 8 : 0;
+    if (avail < 32 + 8 * (uint64_t)n_blocks + record) { return E2BIG; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* const frame = (const uint8_t*)d_frame;
+    uint8_t* const scratch = (uint8_t*)d_scratch;
+    uint32_t* bitmap = (uint32_t*)(scratch + G.bitmap);
+    uint32_t* wpre = (uint32_t*)(scratch + G.wpre);
+    uint64_t* idx_off = (uint64_t*)(scratch + G.misc);
+    uint32_t* idx_crc = (uint32_t*)(scratch + G.misc + 16);
+    uint64_t* spare = (uint64_t*)(scratch + G.misc + 32);
+    uint32_t* ctl = (uint32_t*)(scratch + G.misc + 160);
+    uint32_t* sel = (uint32_t*)(scratch + G.sel);
+    uint64_t* in_off = (uint64_t*)(scratch + G.in_off);
+    uint64_t* out_off = (uint64_t*)(scratch + G.out_off);
+    uint32_t* skip = (uint32_t*)(scratch + G.skip);
+    uint32_t* stored = (uint32_t*)(scratch + G.stored);
+    uint32_t* crc = (uint32_t*)(scratch + G.crc);
+    int32_t* err = (int32_t*)(scratch + G.err);
+    uint64_t* src_off = (uint64_t*)(scratch + G.src_off);
+    uint32_t* mask = (uint32_t*)(scratch + G.mask);
+    uint8_t* blocks = scratch + G.blocks;
+    // the covering blocks as a bitmap, then as a list, with the output's layout and the verdict on the two caps
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_gather_mark(d_offset, d_length, n_ranges, max_length, content_bytes, block_bits, n_blocks, bitmap, st);
+      sqzk::launch_gather_select(bitmap, n_blocks, d_offset, d_length, n_ranges, max_length, content_bytes, m,
+                                 out_capacity, wpre, sel, d_out_off, ctl, st); }
+    // the frame's checks as in frame_decode_dev, and offsets for the list
+    const uint64_t idx_bytes = 8 * (uint64_t)n_blocks + record;
+    sqzk::launch_frame_plan(1, idx_bytes, idx_bytes, 0, idx_off, spare, st);
+    { SpanGuard g(st, SQZ_HIP_K_CRC32);
+      sqzk::launch_crc32_blocks(frame + 32, idx_off, 1, idx_crc, idx_bytes, st); }
+    DictDev dd;
+    uint32_t* dict_crc = nullptr;
+    if (d_dict != NULL) {
+        uint64_t* dict_off = (uint64_t*)(scratch + G.misc + 64);
+        dict_crc = (uint32_t*)(scratch + G.misc + 128);
+        sqzk::launch_frame_plan(1, dict_bytes, dict_bytes, 0, dict_off, dict_off + 4, st);
+        SpanGuard g(st, SQZ_HIP_K_CRC32);
+        sqzk::launch_crc32_blocks((const uint8_t*)d_dict, dict_off, 1, dict_crc, dict_bytes, st);
+        dd.bytes = (const uint8_t*)d_dict; dd.len = (uint32_t)dict_bytes;
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frame_open_list(frame, avail, n_blocks, content_bytes, idx_crc, (uint32_t)dict_bytes, dict_crc, bitmap,
+                                   wpre, sel, ctl, m, in_off, out_off, skip, stored, d_status, d_blocks_decoded, st,
+                                   block_bits); }
+    if (m > 0 && n_ranges > 0) {
+        uint32_t* counts = (uint32_t*)(scratch + G.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + G.codec + align_up((uint64_t)(2 * m) * 4, 256));
+        run_frame_decode(frame, in_off, out_off, 2 * m, 1ull << block_bits, tokens, counts, blocks, err, skip, stored, crc,
+                         dd, st, m);
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_gather_plan(frame, d_offset, d_length, n_ranges, max_length, content_bytes, block_bits, n_blocks,
+                               bitmap, wpre, err, crc, d_status, d_range_err, src_off, mask, st); }
+    if (m > 0 && n_ranges > 0) {
+        SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+        if (max_length <= (uint64_t)sqzk_gather_copy_max) {
+            sqzk::launch_gather_copy(blocks, src_off, (uint8_t*)d_out, d_out_off, d_out_off, mask, n_ranges, st);
+        } else {
+            sqzk::launch_range_copy(blocks, src_off, (uint8_t*)d_out, d_out_off, d_out_off, mask, n_ranges, false,
+                                    max_length, st);
+        }
+    }
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_frame_gather(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                         uint32_t block_bits, const uint64_t* d_offset, const uint64_t* d_length, uint32_t n_ranges,
+                         uint64_t max_length, uint32_t max_blocks, void* d_out, uint64_t out_capacity,
+                         uint64_t* d_out_off, int32_t* d_range_err, uint32_t* d_blocks_decoded, int32_t* d_status,
+                         void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return frame_gather_call(d_frame, avail, n_blocks, content_bytes, block_bits, d_offset, d_length, n_ranges,
+                             max_length, max_blocks, NULL, 0, d_out, out_capacity, d_out_off, d_range_err,
+                             d_blocks_decoded, d_status, d_scratch, scratch_bytes, stream);
+}
+
+int sqz_hip_frame_gather_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                              uint32_t block_bits, const uint64_t* d_offset, const uint64_t* d_length,
+                              uint32_t n_ranges, uint64_t max_length, uint32_t max_blocks, const void* d_dict,
+                              uint64_t dict_bytes, void* d_out, uint64_t out_capacity, uint64_t* d_out_off,
+                              int32_t* d_range_err, uint32_t* d_blocks_decoded, int32_t* d_status, void* d_scratch,
+                              uint64_t scratch_bytes, void* stream) {
+    if (!dict_ok(d_dict, dict_bytes, (uint32_t)sqzk_max_window)) { return EINVAL; }
+    return frame_gather_call(d_frame, avail, n_blocks, content_bytes, block_bits, d_offset, d_length, n_ranges,
+                             max_length, max_blocks, d_dict, dict_bytes, d_out, out_capacity, d_out_off, d_range_err,
+                             d_blocks_decoded, d_status, d_scratch, scratch_bytes, stream);
 }
 
 int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t* d_crc, void* stream) {

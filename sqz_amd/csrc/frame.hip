@@ -450,14 +450,28 @@ void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_block
 // EILSEQ, the payload beyond avail E2BIG.
 // want_bits (either flavour): the block_bits the caller's own arithmetic used, 0 when it used none; a frame with
 // another is EINVAL with the header's other disagreements (a ranged read works first and n_sel out on the host).
-template <bool kDict>
+//
+// kList is the open of a gather (many ranges in one call): the same checks in the same order (first = n_sel = 0),
+// and offsets for the blocks whose bit is set in `bitmap` instead of a run of them.  gather_select_kernel has left
+// wpre (set bits in front of every bitmap word: block b's slot is wpre[b / 32] + popc of the bits below b), sel (the
+// blocks in ascending order), ctl[0] (how many) and ctl[1] (ENOBUFS / ENOSPC / 0).  The decode kernels take a
+// stream as in[in_off[j], in_off[j + 1]), which a selection with gaps cannot give directly, so a slot k has TWO
+// entries: 2k is the block sel[k], 2k + 1 a pseudo-block that covers the bytes up to the next selected stream and
+// is switched off through skip[].  Slot k decodes to [k * block_bytes, ..): a range's covering blocks are
+// consecutive slots, so it lies in one piece.  *status_out = the frame's status, else ctl[1]; *blocks_decoded = 0
+// for a refused frame, else ctl[0].  With any status every one of the 2 * max_blocks entries is empty and skipped,
+// as are the entries behind slot ctl[0] otherwise: the launch behind this one is sized for max_blocks on the host.
+template <bool kDict, bool kList = false>
 __device__ __forceinline__
 void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
                      uint64_t content_bytes, uint32_t first, uint32_t n_sel,
                      const uint32_t* __restrict__ idx_crc, uint64_t* __restrict__ in_off,
                      uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out,
                      uint32_t* __restrict__ stored, uint32_t dict_bytes, const uint32_t* __restrict__ dict_crc,
-                     uint32_t want_bits) {
+                     uint32_t want_bits, const uint32_t* __restrict__ bitmap = nullptr,
+                     const uint32_t* __restrict__ wpre = nullptr, const uint32_t* __restrict__ sel = nullptr,
+                     const uint32_t* __restrict__ ctl = nullptr, uint32_t max_blocks = 0,
+                     uint32_t* __restrict__ skip = nullptr, uint32_t* __restrict__ blocks_decoded = nullptr) {
     __shared__ uint64_t sums[256];
     __shared__ uint32_t wrong[256];
     __shared__ int32_t verdict;
@@ -532,10 +546,52 @@ void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t
                 st = kErrE2BIG;
             }
         }
+        if constexpr (kList) {                     // a frame that holds: the verdict on the two caps
+            *blocks_decoded = st != 0 ? 0u : ctl[0];
+            if (st == 0) { st = (int32_t)ctl[1]; }
+        }
         verdict = st;
         *status_out = st;
     }
     __syncthreads();
+    if constexpr (kList) {
+        const uint64_t entries = 2 * (uint64_t)max_blocks;
+        if (verdict != 0) {                        // refused, or a cap too small: nothing is decoded
+            for (uint64_t k = t; k <= entries; k += 256) {
+                in_off[k] = 0; out_off[k] = 0;
+                if (k < entries) { stored[k] = 0; skip[k] = 1; }
+            }
+            return;
+        }
+        const uint64_t bb = 1ull << block_bits;
+        const uint32_t count = ctl[0];             // <= max_blocks: ctl[1] == 0
+        uint64_t at = payload_off + sums[t];
+        for (uint64_t b = b0; b < b1; b++) {
+            const uint32_t e = index[2 * b];
+            const uint64_t share = (uint64_t)(e & words_mask) * 8;
+            const uint32_t w = bitmap[b >> 5], bit = (uint32_t)b & 31u;
+            if (((w >> bit) & 1u) != 0) {
+                const uint64_t k = wpre[b >> 5] + (uint32_t)__builtin_popcount(w & ((1u << bit) - 1u));
+                if (k < count) {
+                    const uint32_t raw = v2 && (e & kStoredBit) != 0 ? 1u : 0u;
+                    in_off[2 * k] = at; in_off[2 * k + 1] = at + share;
+                    out_off[2 * k] = k * bb; out_off[2 * k + 1] = k * bb + block_len(b, bb, content_bytes);
+                    stored[2 * k] = raw; stored[2 * k + 1] = 0;
+                    skip[2 * k] = raw; skip[2 * k + 1] = 1;
+                }
+            }
+            at += share;
+        }
+        // behind the last slot in use: empty entries at the end of the payload (payload_bytes is the sum: checked)
+        // and at the end of the decoded bytes; entry 2 count - 1 reaches up to them
+        const uint64_t end_in = payload_off + load_le64(frame + 16);
+        const uint64_t end_out = count == 0 ? 0 : (uint64_t)(count - 1) * bb + block_len(sel[count - 1], bb, content_bytes);
+        for (uint64_t k = 2 * (uint64_t)count + t; k <= entries; k += 256) {
+            in_off[k] = end_in; out_off[k] = end_out;
+            if (k < entries) { stored[k] = 0; skip[k] = 1; }
+        }
+        return;
+    }
     if (verdict != 0) {                            // refused: nothing below looks at the index again
         for (uint64_t k = t; k <= n_sel; k += 256) {
             in_off[k] = 0; out_off[k] = 0;
@@ -603,6 +659,50 @@ void launch_frame_open_v3(const uint8_t* frame, uint64_t avail, uint32_t n_block
                           int32_t* status_out, hipStream_t stream, uint32_t want_bits) {
     hipLaunchKernelGGL(frame_open_v3_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
                        first, n_sel, idx_crc, in_off, out_off, status_out, stored, dict_bytes, dict_crc, want_bits);
+}
+
+__global__ __launch_bounds__(256)
+void frame_open_list_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
+                            uint64_t content_bytes, const uint32_t* __restrict__ idx_crc,
+                            const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ wpre,
+                            const uint32_t* __restrict__ sel, const uint32_t* __restrict__ ctl, uint32_t max_blocks,
+                            uint64_t* __restrict__ in_off, uint64_t* __restrict__ out_off,
+                            uint32_t* __restrict__ skip, uint32_t* __restrict__ stored,
+                            int32_t* __restrict__ status_out, uint32_t* __restrict__ blocks_decoded,
+                            uint32_t want_bits) {
+    frame_open_body<false, true>(frame, avail, n_blocks, content_bytes, 0u, 0u, idx_crc, in_off, out_off, status_out,
+                                 stored, 0u, nullptr, want_bits, bitmap, wpre, sel, ctl, max_blocks, skip,
+                                 blocks_decoded);
+}
+
+__global__ __launch_bounds__(256)
+void frame_open_list_v3_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
+                               uint64_t content_bytes, const uint32_t* __restrict__ idx_crc,
+                               const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ wpre,
+                               const uint32_t* __restrict__ sel, const uint32_t* __restrict__ ctl, uint32_t max_blocks,
+                               uint64_t* __restrict__ in_off, uint64_t* __restrict__ out_off,
+                               uint32_t* __restrict__ skip, uint32_t* __restrict__ stored,
+                               int32_t* __restrict__ status_out, uint32_t* __restrict__ blocks_decoded,
+                               uint32_t dict_bytes, const uint32_t* __restrict__ dict_crc, uint32_t want_bits) {
+    frame_open_body<true, true>(frame, avail, n_blocks, content_bytes, 0u, 0u, idx_crc, in_off, out_off, status_out,
+                                stored, dict_bytes, dict_crc, want_bits, bitmap, wpre, sel, ctl, max_blocks, skip,
+                                blocks_decoded);
+}
+
+void launch_frame_open_list(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                            const uint32_t* idx_crc, uint32_t dict_bytes, const uint32_t* dict_crc,
+                            const uint32_t* bitmap, const uint32_t* wpre, const uint32_t* sel, const uint32_t* ctl,
+                            uint32_t max_blocks, uint64_t* in_off, uint64_t* out_off, uint32_t* skip, uint32_t* stored,
+                            int32_t* status_out, uint32_t* blocks_decoded, hipStream_t stream, uint32_t want_bits) {
+    if (dict_crc != nullptr) {
+        hipLaunchKernelGGL(frame_open_list_v3_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks,
+                           content_bytes, idx_crc, bitmap, wpre, sel, ctl, max_blocks, in_off, out_off, skip, stored,
+                           status_out, blocks_decoded, dict_bytes, dict_crc, want_bits);
+    } else {
+        hipLaunchKernelGGL(frame_open_list_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks,
+                           content_bytes, idx_crc, bitmap, wpre, sel, ctl, max_blocks, in_off, out_off, skip, stored,
+                           status_out, blocks_decoded, want_bits);
+    }
 }
 
 // err[k] for the selected blocks: the frame's status where it was refused; EILSEQ where the decoder was
@@ -740,6 +840,263 @@ void launch_range_copy(const uint8_t* src, const uint64_t* src_off, uint8_t* dst
     while (groups > 1 && groups * n_ranges > 0x7FFFFFFFull) { groups /= 2; }
     hipLaunchKernelGGL(range_copy_kernel, dim3((unsigned)(groups * n_ranges)), dim3(kCopyThreads), 0, stream,
                        src, src_off, dst, dst_off, len_off, mask, n_ranges, pad8 ? 1u : 0u, (uint32_t)groups);
+}
+
+// ---------------------------------------------------------------------------------------- gather
+// Many byte ranges of a resident frame in one call ("Gather").  offset[] and length[] lie in
+// device memory; the host knows their number, max_length (a cap on every length) and max_blocks (a cap on the
+// distinct covering blocks).  mark -> select -> open for a list (frame_open_body<.., true>) -> the decode chain ->
+// plan -> copy.
+constexpr int kErrENOBUFS = 105, kErrENOSPC = 28;  // <errno.h>, checked in abi.hip
+constexpr int kGatherThreads = 256;
+
+// a range the call delivers: no longer than the cap, inside the content, offset + length without a wrap
+__device__ __forceinline__ bool gather_range_ok(uint64_t off, uint64_t len, uint64_t max_length,
+                                                uint64_t content_bytes) {
+    return len <= max_length && off <= content_bytes && len <= content_bytes - off;
+}
+
+// One lane per range: the bits of its covering blocks into bitmap (n_blocks bits, zero at the start), a word at a
+// time.  max_length bounds the loop: ((max_length + 2^b - 2) >> b) + 1 blocks at the most, 32 to a word.
+__global__ __launch_bounds__(kGatherThreads)
+void gather_mark_kernel(const uint64_t* __restrict__ offset, const uint64_t* __restrict__ length, uint32_t n_ranges,
+                        uint64_t max_length, uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks,
+                        uint32_t* __restrict__ bitmap) {
+    const uint64_t r = (uint64_t)blockIdx.x * kGatherThreads + threadIdx.x;
+    if (r >= n_ranges) { return; }
+    const uint64_t off = offset[r], len = length[r];
+    if (len == 0 || !gather_range_ok(off, len, max_length, content_bytes)) { return; }
+    const uint64_t first = off >> block_bits;
+    uint64_t last = (off + len - 1) >> block_bits;
+    if (first >= n_blocks) { return; }             // (n_blocks is ceil(content / 2^b), the call checked: never taken)
+    if (last >= n_blocks) { last = (uint64_t)n_blocks - 1; }
+    for (uint64_t w = first >> 5; w <= last >> 5; w++) {
+        const uint32_t lo = w == first >> 5 ? (uint32_t)first & 31u : 0u;
+        const uint32_t hi = w == last >> 5 ? (uint32_t)last & 31u : 31u;
+        const uint32_t bits = (0xFFFFFFFFu >> (31u - hi)) & (0xFFFFFFFFu << lo);
+#ifdef SQZ_WAVE_EMU
+        bitmap[w] |= bits;                         // lanes run one after the other there: a plain read-modify-write
+#else
+        atomicOr(&bitmap[w], bits);
+#endif
+    }
+}
+
+void launch_gather_mark(const uint64_t* offset, const uint64_t* length, uint32_t n_ranges, uint64_t max_length,
+                        uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks, uint32_t* bitmap,
+                        hipStream_t stream) {
+    const uint64_t words = ((uint64_t)n_blocks + 31) / 32;
+#ifdef SQZ_WAVE_EMU
+    memset(bitmap, 0, (size_t)words * 4);
+#else
+    if (words > 0) { (void)hipMemsetAsync(bitmap, 0, (size_t)words * 4, stream); }
+#endif
+    if (n_ranges == 0) { return; }
+    const uint64_t grid = ((uint64_t)n_ranges + kGatherThreads - 1) / kGatherThreads;
+    hipLaunchKernelGGL(gather_mark_kernel, dim3((unsigned)grid), dim3(kGatherThreads), 0, stream, offset, length,
+                       n_ranges, max_length, content_bytes, block_bits, n_blocks, bitmap);
+}
+
+// One workgroup, two scans.  The bitmap: wpre[w] = set bits in front of word w (wpre[words] = all of them) and
+// sel[k] = the k-th set bit, ascending, for k < max_blocks -- nothing is written behind the cap.  The ranges:
+// out_off = the exclusive prefix sum of the valid ranges' lengths (n_ranges + 1 entries); it depends on the ranges
+// alone.  ctl[0] = the distinct covering blocks; ctl[1] = ENOBUFS when they are more than max_blocks, else ENOSPC
+// when the lengths add up to more than out_capacity (or to more than 64 bits hold), else 0.
+__global__ __launch_bounds__(kGatherThreads)
+void gather_select_kernel(const uint32_t* __restrict__ bitmap, uint32_t n_blocks,
+                          const uint64_t* __restrict__ offset, const uint64_t* __restrict__ length, uint32_t n_ranges,
+                          uint64_t max_length, uint64_t content_bytes, uint32_t max_blocks, uint64_t out_capacity,
+                          uint32_t* __restrict__ wpre, uint32_t* __restrict__ sel, uint64_t* __restrict__ out_off,
+                          uint32_t* __restrict__ ctl) {
+    __shared__ uint64_t sums[kGatherThreads];
+    __shared__ uint32_t cnts[kGatherThreads];
+    __shared__ uint32_t wraps[kGatherThreads];
+    const uint32_t t = threadIdx.x;
+    const uint64_t words = ((uint64_t)n_blocks + 31) / 32;
+    const uint64_t per_w = (words + kGatherThreads - 1) / kGatherThreads;
+    const uint64_t w0 = t * per_w < words ? t * per_w : words;
+    const uint64_t w1 = w0 + per_w < words ? w0 + per_w : words;
+    const uint64_t per_r = ((uint64_t)n_ranges + kGatherThreads - 1) / kGatherThreads;
+    const uint64_t r0 = t * per_r < n_ranges ? t * per_r : n_ranges;
+    const uint64_t r1 = r0 + per_r < n_ranges ? r0 + per_r : n_ranges;
+    uint32_t cnt = 0;
+    for (uint64_t w = w0; w < w1; w++) { cnt += (uint32_t)__builtin_popcount(bitmap[w]); }
+    uint64_t sum = 0;
+    uint32_t wrapped = 0;
+    for (uint64_t r = r0; r < r1; r++) {
+        const uint64_t len = length[r];
+        if (gather_range_ok(offset[r], len, max_length, content_bytes)) {
+            if (len > ~sum) { wrapped = 1; }
+            sum += len;
+        }
+    }
+    cnts[t] = cnt;
+    sums[t] = sum;
+    wraps[t] = wrapped;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t c = 0, over = 0;
+        uint64_t run = 0;
+        for (int k = 0; k < kGatherThreads; k++) {
+            const uint32_t v = cnts[k];
+            cnts[k] = c;
+            c += v;
+            const uint64_t s = sums[k];
+            sums[k] = run;
+            if (s > ~run) { over = 1; }
+            over |= wraps[k];
+            run += s;
+        }
+        ctl[0] = c;
+        ctl[1] = c > max_blocks ? (uint32_t)kErrENOBUFS : (over != 0 || run > out_capacity ? (uint32_t)kErrENOSPC : 0u);
+        wpre[words] = c;
+        out_off[n_ranges] = run;
+    }
+    __syncthreads();
+    uint32_t k = cnts[t];
+    for (uint64_t w = w0; w < w1; w++) {
+        uint32_t word = bitmap[w];
+        wpre[w] = k;
+        while (word != 0) {
+            if (k < max_blocks) { sel[k] = (uint32_t)(w * 32) + (uint32_t)__builtin_ctz(word); }
+            k++;
+            word &= word - 1;
+        }
+    }
+    uint64_t at = sums[t];
+    for (uint64_t r = r0; r < r1; r++) {
+        const uint64_t len = length[r];
+        out_off[r] = at;
+        if (gather_range_ok(offset[r], len, max_length, content_bytes)) { at += len; }
+    }
+}
+
+void launch_gather_select(const uint32_t* bitmap, uint32_t n_blocks, const uint64_t* offset, const uint64_t* length,
+                          uint32_t n_ranges, uint64_t max_length, uint64_t content_bytes, uint32_t max_blocks,
+                          uint64_t out_capacity, uint32_t* wpre, uint32_t* sel, uint64_t* out_off, uint32_t* ctl,
+                          hipStream_t stream) {
+    hipLaunchKernelGGL(gather_select_kernel, dim3(1), dim3(kGatherThreads), 0, stream, bitmap, n_blocks, offset,
+                       length, n_ranges, max_length, content_bytes, max_blocks, out_capacity, wpre, sel, out_off, ctl);
+}
+
+// One lane per range, once the selected blocks lie decoded in the scratch (entry 2k of err and crc is slot k's, as
+// frame_open_body<.., true> laid them out).  range_err[r]: EINVAL for an invalid range; the call's status where it
+// is not 0; otherwise the first non-zero errno among the covering blocks in ascending order -- what the decoder
+// said, or EILSEQ where it was content but the bytes are not the ones the index entry's CRC-32 was taken of.  And
+// the range's entry in the copy's work list: where it starts in the decoded blocks (its blocks are consecutive
+// slots) and whether it is delivered; destination and length are the caller's out_off.
+__global__ __launch_bounds__(kGatherThreads)
+void gather_plan_kernel(const uint8_t* __restrict__ frame, const uint64_t* __restrict__ offset,
+                        const uint64_t* __restrict__ length, uint32_t n_ranges, uint64_t max_length,
+                        uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks,
+                        const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ wpre,
+                        const int32_t* __restrict__ err, const uint32_t* __restrict__ crc,
+                        const int32_t* __restrict__ status, int32_t* __restrict__ range_err,
+                        uint64_t* __restrict__ src_off, uint32_t* __restrict__ mask) {
+    const uint64_t r = (uint64_t)blockIdx.x * kGatherThreads + threadIdx.x;
+    if (r >= n_ranges) { return; }
+    const uint64_t off = offset[r], len = length[r];
+    if (!gather_range_ok(off, len, max_length, content_bytes)) {
+        range_err[r] = kErrEINVAL; src_off[r] = 0; mask[r] = 0;
+        return;
+    }
+    int32_t e = *status;
+    uint64_t at = 0;
+    const uint64_t first = off >> block_bits;
+    if (e == 0 && len > 0 && first < n_blocks) {
+        uint64_t last = (off + len - 1) >> block_bits;
+        if (last >= n_blocks) { last = (uint64_t)n_blocks - 1; }
+        const uint32_t w = bitmap[first >> 5], bit = (uint32_t)first & 31u;
+        const uint64_t k0 = wpre[first >> 5] + (uint32_t)__builtin_popcount(w & ((1u << bit) - 1u));
+        const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
+        for (uint64_t b = first; b <= last && e == 0; b++) {
+            const uint64_t k = k0 + (b - first);
+            e = err[2 * k];
+            if (e == 0 && crc[2 * k] != index[2 * b + 1]) { e = kErrEILSEQ; }
+        }
+        at = (k0 << block_bits) + (off & ((1ull << block_bits) - 1));
+    }
+    range_err[r] = e;
+    src_off[r] = at;
+    mask[r] = e == 0 && len > 0 ? 1u : 0u;
+}
+
+void launch_gather_plan(const uint8_t* frame, const uint64_t* offset, const uint64_t* length, uint32_t n_ranges,
+                        uint64_t max_length, uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks,
+                        const uint32_t* bitmap, const uint32_t* wpre, const int32_t* err, const uint32_t* crc,
+                        const int32_t* status, int32_t* range_err, uint64_t* src_off, uint32_t* mask,
+                        hipStream_t stream) {
+    if (n_ranges == 0) { return; }
+    const uint64_t grid = ((uint64_t)n_ranges + kGatherThreads - 1) / kGatherThreads;
+    hipLaunchKernelGGL(gather_plan_kernel, dim3((unsigned)grid), dim3(kGatherThreads), 0, stream, frame, offset,
+                       length, n_ranges, max_length, content_bytes, block_bits, n_blocks, bitmap, wpre, err, crc,
+                       status, range_err, src_off, mask);
+}
+
+// range_copy_kernel's row load as a function of its own (the kernel above keeps its text, and with it its registers):
+// the 16 source bytes at sp of a range [from, src_end), sh = sp & 15: one aligned load when the sides share the
+// alignment, two aligned loads joined by a byte shift when both source rows lie inside the range, single bytes otherwise
+__device__ __forceinline__ uint4 load_shifted_row(const uint8_t* sp, uint32_t sh, const uint8_t* from,
+                                                  const uint8_t* src_end) {
+    uint4 v;
+    if (sh == 0) {
+        v = *reinterpret_cast<const uint4*>(sp);
+    } else if (sp - sh >= from && sp - sh + 32 <= src_end) {
+        const uint4 a = *reinterpret_cast<const uint4*>(sp - sh);
+        const uint4 c = *reinterpret_cast<const uint4*>(sp - sh + 16);
+        const uint64_t q0 = (uint64_t)a.x | ((uint64_t)a.y << 32), q1 = (uint64_t)a.z | ((uint64_t)a.w << 32);
+        const uint64_t q2 = (uint64_t)c.x | ((uint64_t)c.y << 32), q3 = (uint64_t)c.z | ((uint64_t)c.w << 32);
+        const bool up = sh >= 8;
+        const uint32_t s = sh & 7u;
+        const uint64_t lo = join_bytes(up ? q1 : q0, up ? q2 : q1, s);
+        const uint64_t hi = join_bytes(up ? q2 : q1, up ? q3 : q2, s);
+        v.x = (uint32_t)lo; v.y = (uint32_t)(lo >> 32); v.z = (uint32_t)hi; v.w = (uint32_t)(hi >> 32);
+    } else {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};           // a source row that is not whole inside the range: byte by byte
+#pragma unroll
+        for (uint32_t j = 0; j < 16; j++) { w[j >> 2] |= (uint32_t)sp[j] << (8 * (j & 3)); }
+        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    }
+    return v;
+}
+
+// range_copy_kernel's work list and rules (nothing outside a source range is read, nothing outside a destination
+// range is written, any alignment on either side) for many short ranges: kGatherLanes lanes per range instead of a
+// workgroup, so a 256-byte range is one row per lane and a workgroup moves 16 ranges.  No padding.
+constexpr uint32_t kGatherLanes = 16;
+
+__global__ __launch_bounds__(kCopyThreads)
+void gather_copy_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
+                        uint8_t* __restrict__ dst, const uint64_t* __restrict__ dst_off,
+                        const uint64_t* __restrict__ len_off, const uint32_t* __restrict__ mask, uint32_t n_ranges) {
+    const uint64_t b = (uint64_t)blockIdx.x * (kCopyThreads / kGatherLanes) + threadIdx.x / kGatherLanes;
+    if (b >= n_ranges) { return; }
+    if (mask != nullptr && mask[b] == 0) { return; }
+    const uint32_t lane = threadIdx.x % kGatherLanes;
+    const uint64_t l0 = len_off[b], l1 = len_off[b + 1];
+    const uint64_t len = l1 > l0 ? l1 - l0 : 0;
+    const uint8_t* const from = src + src_off[b];
+    uint8_t* const to = dst + dst_off[b];
+    uint64_t head = (16u - (uint32_t)((uintptr_t)to & 15u)) & 15u;     // bytes in front of the first full row
+    if (head > len) { head = len; }
+    const uint64_t rows = (len - head) / 16;
+    const uint64_t tail_at = head + 16 * rows;                         // fewer than 16 bytes behind the last full row
+    if (lane < head) { to[lane] = from[lane]; }
+    if (lane < len - tail_at) { to[tail_at + lane] = from[tail_at + lane]; }
+    const uint8_t* const fb = from + head;
+    uint8_t* const tb = to + head;                                     // 16-byte aligned
+    const uint32_t sh = (uint32_t)((uintptr_t)fb & 15u);
+    for (uint64_t k = lane; k < rows; k += kGatherLanes) {
+        *reinterpret_cast<uint4*>(tb + 16 * k) = load_shifted_row(fb + 16 * k, sh, from, from + len);
+    }
+}
+
+void launch_gather_copy(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, const uint64_t* dst_off,
+                        const uint64_t* len_off, const uint32_t* mask, uint32_t n_ranges, hipStream_t stream) {
+    if (n_ranges == 0) { return; }
+    const uint64_t per = kCopyThreads / kGatherLanes;
+    hipLaunchKernelGGL(gather_copy_kernel, dim3((unsigned)(((uint64_t)n_ranges + per - 1) / per)), dim3(kCopyThreads),
+                       0, stream, src, src_off, dst, dst_off, len_off, mask, n_ranges);
 }
 
 } // namespace sqzk

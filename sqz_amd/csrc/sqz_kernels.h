@@ -146,4 +146,37 @@ void launch_frame_read_plan(const int32_t* err, uint32_t n_sel, uint64_t src_at,
 void launch_frame_verify(const uint8_t* frame, uint32_t first, uint32_t n_sel, const uint32_t* crc,
                          const int32_t* status, int32_t* err, hipStream_t stream);
 
+// many ranges of a resident frame in one call (frame.hip, "gather").  offset / length:
+// n_ranges device values each; a range is valid iff length <= max_length, offset <= content_bytes and
+// length <= content_bytes - offset.
+// mark: zeroes bitmap (ceil(n_blocks / 32) words) and sets the bits of the valid ranges' covering blocks.
+// select: wpre (words + 1 entries), sel (max_blocks entries, ascending), out_off (n_ranges + 1: the prefix sum of the
+//   valid lengths), ctl[0] = the distinct blocks, ctl[1] = ENOBUFS / ENOSPC / 0 (ctl: 2 words).
+// open_list: the checks of launch_frame_open_v2 (dict_crc == nullptr) or launch_frame_open_v3, then TWO entries per
+//   slot in in_off / out_off (2 max_blocks + 1 entries), skip and stored (2 max_blocks): entry 2k is block sel[k],
+//   decoded to [k << block_bits, ..), entry 2k + 1 the skipped gap up to the next selected stream.  *status_out =
+//   the frame's status, else ctl[1]; *blocks_decoded = 0 for a refused frame, else ctl[0].
+// plan: range_err, and src_off / mask for the copy of range r to dst + out_off[r] (len_off = dst_off = out_off);
+//   err / crc: the decode chain's, 2 max_blocks entries.
+// gather_copy: launch_range_copy's work list with 16 lanes per range, for many short ranges; never pads.
+void launch_gather_mark(const uint64_t* offset, const uint64_t* length, uint32_t n_ranges, uint64_t max_length,
+                        uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks, uint32_t* bitmap,
+                        hipStream_t stream);
+void launch_gather_select(const uint32_t* bitmap, uint32_t n_blocks, const uint64_t* offset, const uint64_t* length,
+                          uint32_t n_ranges, uint64_t max_length, uint64_t content_bytes, uint32_t max_blocks,
+                          uint64_t out_capacity, uint32_t* wpre, uint32_t* sel, uint64_t* out_off, uint32_t* ctl,
+                          hipStream_t stream);
+void launch_frame_open_list(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                            const uint32_t* idx_crc, uint32_t dict_bytes, const uint32_t* dict_crc,
+                            const uint32_t* bitmap, const uint32_t* wpre, const uint32_t* sel, const uint32_t* ctl,
+                            uint32_t max_blocks, uint64_t* in_off, uint64_t* out_off, uint32_t* skip, uint32_t* stored,
+                            int32_t* status_out, uint32_t* blocks_decoded, hipStream_t stream, uint32_t want_bits);
+void launch_gather_plan(const uint8_t* frame, const uint64_t* offset, const uint64_t* length, uint32_t n_ranges,
+                        uint64_t max_length, uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks,
+                        const uint32_t* bitmap, const uint32_t* wpre, const int32_t* err, const uint32_t* crc,
+                        const int32_t* status, int32_t* range_err, uint64_t* src_off, uint32_t* mask,
+                        hipStream_t stream);
+void launch_gather_copy(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, const uint64_t* dst_off,
+                        const uint64_t* len_off, const uint32_t* mask, uint32_t n_ranges, hipStream_t stream);
+
 } // namespace sqzk

@@ -327,6 +327,81 @@ def read_frame(d_frame, offset: int, length: int, d_out=None, info: dict = None,
     return d_out[:length], err[:covering], status
 
 
+def _ranges_dev(values, device, what):
+    """a list of offsets or lengths as a uint64 device tensor's bits: (tensor, host list or None)"""
+    import torch
+    if isinstance(values, torch.Tensor):
+        if values.dim() != 1 or values.dtype not in (torch.int64, torch.uint64):
+            raise ValueError(f"gather_frame: {what} must be a one-dimensional int64 or uint64 tensor")
+        return values.contiguous().to(device), None
+    host = [int(v) for v in values]
+    if any(v < 0 or v >> 64 for v in host):
+        raise ValueError(f"gather_frame: {what} must be 0 .. 2^64 - 1")
+    signed = [v - (1 << 64) if v >> 63 else v for v in host]
+    return torch.tensor(signed, dtype=torch.int64, device=device), host
+
+
+def gather_bound(n_blocks: int, n_ranges: int, max_length: int, block_bits: int) -> int:
+    """a max_blocks that is always enough: every range at a block's last byte, no block shared"""
+    return min(n_blocks, n_ranges * (((max_length + (1 << block_bits) - 2) >> block_bits) + 1))
+
+
+def gather_frame(d_frame, offsets, lengths, max_length: int = None, max_blocks: int = None, d_out=None,
+                 info: dict = None, dictionary=None, scratch=None):
+    """Many byte ranges of a device-resident frame in one call: content[offsets[r] : offsets[r] + lengths[r]] for every
+    r, packed in request order into d_out (uint8, made when not given).  Every distinct covering block is decoded once,
+    into the scratch, and verified.  offsets / lengths: int64 or uint64 device tensors, which the host never reads --
+    max_length, a hard cap on every length, is then required -- or sequences, which are uploaded; max_length may then
+    be worked out here, and a range that is longer than it or leaves the content raises ValueError here.  max_blocks:
+    a cap on the distinct covering blocks, by default gather_bound(), which is always enough.  `info` and dictionary
+    as for read_frame.
+    Enqueues and returns (d_out, out_off int64[n + 1], range_err int32[n], blocks_decoded int32[1], status int32[1]),
+    all device tensors: range r lies at d_out[out_off[r] : out_off[r + 1]] when status and range_err[r] are 0 after a
+    synchronise.  A range the device finds invalid has range_err EINVAL and length 0; status ENOBUFS / ENOSPC say that
+    max_blocks / d_out were too small (blocks_decoded and out_off[n] say what it takes), anything else is the frame's
+    own status; a block that fails costs the ranges that touch it (their range_err) and nothing else."""
+    import torch
+    L = N.lib()
+    if info is None:
+        info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    n, content, bits = info["n_blocks"], info["content_bytes"], info["block_bytes"].bit_length() - 1
+    device = d_frame.device
+    d = _dict_dev(dictionary, 1 << info["win_bits"], device) if dictionary is not None else None
+    d_offsets, h_offsets = _ranges_dev(offsets, device, "offsets")
+    d_lengths, h_lengths = _ranges_dev(lengths, device, "lengths")
+    count = d_offsets.numel()
+    if d_lengths.numel() != count:
+        raise ValueError("gather_frame: as many lengths as offsets")
+    if max_length is None:
+        if h_lengths is None:
+            raise ValueError("gather_frame: max_length is required when the lengths are a device tensor")
+        max_length = max(h_lengths, default=0)
+    if h_offsets is not None and h_lengths is not None:
+        for o, ln in zip(h_offsets, h_lengths):
+            if ln > max_length or o > content or ln > content - o:
+                raise ValueError(f"gather_frame: range ({o}, {ln}) is longer than max_length or leaves the content")
+    if max_blocks is None:
+        max_blocks = gather_bound(n, count, max_length, bits)
+    if d_out is None:
+        total = sum(h_lengths) if h_lengths is not None else count * max_length
+        d_out = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+    out_off = torch.zeros(count + 1, dtype=torch.int64, device=device)
+    range_err = torch.zeros(max(count, 1), dtype=torch.int32, device=device)
+    blocks_decoded = torch.zeros(1, dtype=torch.int32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    if scratch is None:
+        scratch = _scratch_for(device, int(L.sqz_hip_frame_gather_scratch_bytes(n, count, max_blocks, bits)))
+    head = (_ptr(d_frame), d_frame.numel(), n, content, bits, _ptr(d_offsets), _ptr(d_lengths), count, max_length,
+            max_blocks)
+    tail = (_ptr(d_out), d_out.numel(), _ptr(out_off), _ptr(range_err), _ptr(blocks_decoded), _ptr(status),
+            _ptr(scratch), scratch.numel(), _stream())
+    if d is not None:
+        _raise(L.sqz_hip_frame_gather_dict(*head, _ptr(d), d.numel(), *tail), "sqz_hip_frame_gather_dict")
+    else:
+        _raise(L.sqz_hip_frame_gather(*head, *tail), "sqz_hip_frame_gather")
+    return d_out, out_off, range_err[:count], blocks_decoded, status
+
+
 # ---- file tool ----------------------------------------------------------------------------------
 def main(argv=None) -> int:
     import argparse
