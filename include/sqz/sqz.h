@@ -689,6 +689,80 @@ SQZ_API int sqz_hip_frame_gather_dict(const void* d_frame, uint64_t avail, uint3
                                       int32_t* d_range_err, uint32_t* d_blocks_decoded, int32_t* d_status,
                                       void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* Many byte ranges WRITTEN into a resident frame in one call: the mirror of sqz_hip_frame_gather, and its conventions
+ * (device pointers; d_frame, d_new_frame and d_scratch 16-byte aligned; asynchronous, no host synchronisation inside;
+ * n_blocks, content_bytes, win_bits and block_bits from a host copy of the header -- win_bits because the encoder's
+ * launches take the window from the host; d_offset and d_length in DEVICE memory, never read by the host; n_ranges,
+ * max_length and max_blocks as for the gather, validity of a range by the gather's rule).  sqz_hip_frame_update is
+ * for versions 1 and 2, _update_dict for version 3.
+ *
+ * d_data (data_bytes of it) holds the bytes to write, packed in request order; d_data_off (n_ranges + 1 entries) is
+ * WRITTEN by the call: the exclusive prefix sum of the valid ranges' lengths.  It depends on the ranges alone and is
+ * written even when the frame is refused, exactly like the gather's d_out_off.  Range r takes
+ * d_data[d_data_off[r], d_data_off[r + 1]) to content[offset[r], offset[r] + length[r]).  Where two valid ranges overlap,
+ * each overlapped byte takes the value of one of them, unspecified which (the rule of an indexed scatter); a block's
+ * checksum is taken after the patch, so the frame is consistent either way.  parse: SQZ_PARSE_GREEDY or SQZ_PARSE_LAZY,
+ * for the blocks that are encoded again.
+ *
+ * The new frame (d_new_frame, at most `capacity` bytes, *d_frame_bytes its size) keeps the old one's version, win_bits,
+ * block_bits, flags, content_bytes and, in version 3, the dictionary's record: content length never changes.  Only the
+ * DISTINCT covering blocks are touched: each is decoded into the scratch and verified against its CRC-32, patched,
+ * checksummed again, encoded, and in a frame of version 2, or of version 3 with SQZ_FRAME_STORED, stored when its
+ * stream is not smaller than its content (the writer's rule).  Every other block is KEPT: its index entry and its
+ * stream are copied as they are, neither decoded nor verified -- a damaged kept block stays damaged and is still
+ * reported by a later decode.  On status 0 the new frame is byte for byte what the encoder of that version writes for
+ * the patched content with the same parse, provided the kept streams were written with that parse too.
+ *
+ * *d_status is the first of these that applies, and with ANY non-zero status not one byte of d_new_frame is written:
+ *   1. the frame's own status: the checks of sqz_hip_frame_gather / _gather_dict in their order, then EINVAL for a
+ *      frame whose win_bits is not the argument.  *d_blocks_encoded = 0.
+ *   2. ERANGE: at least one range is invalid.  Those ranges have d_range_err[r] = EINVAL (every other one 0) and count
+ *      as length 0 in d_data_off.  A write call does not silently drop a write: it refuses the lot.
+ *   3. ENOBUFS: more distinct covering blocks than max_blocks.
+ *   4. ENODATA: d_data_off[n_ranges] > data_bytes.
+ *   5. the first non-zero errno among the touched blocks in ascending order: the decoder's, or EILSEQ for a checksum
+ *      that does not hold.  The call does not build on content it cannot verify.
+ *   6. a touched block's encoder errno (the first in ascending order).
+ *   7. E2BIG: the new frame does not fit capacity; *d_frame_bytes is the size it takes.
+ *   *d_frame_bytes is the frame's size for status 0 and for 7, and 0 for 1 to 6.  Under 1 to 4 nothing is decoded.
+ *   *d_blocks_encoded is the number of distinct covering blocks of the valid ranges in every case but 1 (under 3: what
+ *   to ask for).  A capacity of sqz_frame_bound / _bound_ex / _bound_dict for the frame's version is always enough.
+ * n_ranges == 0 writes d_data_off[0] = 0 and a copy of the old frame (its exact bytes), or the frame's status.
+ * EINVAL at the call, nothing enqueued: the gather's list (d_data_off for d_out_off, d_blocks_encoded for
+ *   d_blocks_decoded; data_bytes > 0 with a null d_data for its d_out rule); win_bits outside 10..15; a null or
+ *   misaligned d_new_frame; a null d_frame_bytes; [d_new_frame, + capacity) overlapping [d_frame, + avail) or the
+ *   scratch; a parse that is none; a scratch smaller than the function says; _dict: d_dict == NULL or dict_bytes outside
+ *   1 .. 2^win_bits - 1.  E2BIG when avail does not cover header and index (and record), ENODEV without a device.
+ * Scratch, with m = min(max_blocks, n_blocks), w = ceil(n_blocks / 32), D = dict_bytes (0 for versions 1 and 2), every
+ * term rounded up to 256:
+ *       sqz_hip_frame_update_scratch_bytes(n_blocks, n_ranges, max_blocks, b, D) =
+ *           2 * (4 w + 4) + 256 + (4 m + 4) + 2 * 8 (2 m + 1) + 4 * (8 m + 4) + (8 n_ranges + 8) + (4 n_ranges + 4)
+ *           + ((m << b) + 16)                                         [so far the gather's terms without its decoder]
+ *           + (8 n_ranges + 8) + 2 * 8 (m + 1) + (8 m + 8) + 2 * (4 m + 4)
+ *           + 8 (2 m + 2) + 2 * 8 (2 m + 1) + 256 + (D > 0 ? 256 + 2 * round_up_256(4 * (D + 64)) : 0)
+ *           + m * sqz_bound(2^b)
+ *           + max(sqz_hip_decode_scratch_bytes(2 m, m << b), sqz_hip_encode_scratch_bytes(m, m << b))
+ *   (the patch's destinations, the encoder's two offset lists, its sizes, errnos and the new checksums per slot, the
+ *   three columns of the segment table, the verdict words, the dictionary's index, m slabs, and the encoder's scratch
+ *   over the decoder's, which is done by then); 0 for a bad block_bits or D > 32767.                                   */
+SQZ_API uint64_t sqz_hip_frame_update_scratch_bytes(uint32_t n_blocks, uint32_t n_ranges, uint32_t max_blocks,
+                                                    uint32_t block_bits, uint64_t dict_bytes);
+SQZ_API int sqz_hip_frame_update(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                 uint32_t win_bits, uint32_t block_bits, const uint64_t* d_offset,
+                                 const uint64_t* d_length, uint32_t n_ranges, uint64_t max_length, uint32_t max_blocks,
+                                 const void* d_data, uint64_t data_bytes, uint64_t* d_data_off, uint32_t parse,
+                                 void* d_new_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_range_err,
+                                 uint32_t* d_blocks_encoded, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                 void* stream);
+SQZ_API int sqz_hip_frame_update_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                      uint32_t win_bits, uint32_t block_bits, const uint64_t* d_offset,
+                                      const uint64_t* d_length, uint32_t n_ranges, uint64_t max_length,
+                                      uint32_t max_blocks, const void* d_data, uint64_t data_bytes, uint64_t* d_data_off,
+                                      uint32_t parse, const void* d_dict, uint64_t dict_bytes, void* d_new_frame,
+                                      uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_range_err,
+                                      uint32_t* d_blocks_encoded, int32_t* d_status, void* d_scratch,
+                                      uint64_t scratch_bytes, void* stream);
+
 /* Live timing of the last kernels enqueued through this library on the
  * calling thread's context, measured with HIP events ON THE LAUNCH STREAM.
  * Enabled with sqz_hip_set_timing(1); values in milliseconds.               */
@@ -705,8 +779,8 @@ enum {
     SQZ_HIP_K_RC_ENCODE = 7,      /* rc_encode_kernel  } R-era range coder            */
     SQZ_HIP_K_RC_DECODE = 8,      /* rc_decode_kernel  } (include/sqz/sqz_rc.h)       */
     SQZ_HIP_K_CRC32 = 9,          /* crc32_blocks_kernel } SQZF frames                */
-    SQZ_HIP_K_FRAME_INDEX = 10,   /* frame_index_kernel / frame_open_kernel }         */
-    SQZ_HIP_K_RANGE_COPY = 11,    /* range_copy_kernel: stored blocks (SQZF version 2) */
+    SQZ_HIP_K_FRAME_INDEX = 10,   /* frame_index_kernel / frame_open_kernel } (and an update's planning) */
+    SQZ_HIP_K_RANGE_COPY = 11,    /* range_copy_kernel: stored blocks (SQZF version 2); frame_splice_kernel */
     SQZ_HIP_KERNELS = 12
 };
 typedef struct sqz_hip_timing {

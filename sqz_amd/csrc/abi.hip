@@ -517,6 +517,7 @@ int decode_host(Lane& c, hipStream_t st, const uint8_t* in, const uint64_t* in_o
 // ---------------------------------------------------------------- SQZF frames (include/sqz/sqz.h)
 static_assert(EINVAL == 22 && E2BIG == 7 && EILSEQ == 84, "frame.hip writes these errno values from the device");
 static_assert(ENOBUFS == 105 && ENOSPC == 28, "frame.hip writes these errno values from the device");
+static_assert(ERANGE == 34 && ENODATA == 61, "frame.hip writes these errno values from the device");
 
 uint32_t get_le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint64_t get_le64(const uint8_t* p) { return (uint64_t)get_le32(p) | ((uint64_t)get_le32(p + 4) << 32); }
@@ -2089,7 +2090,9 @@ int sqz_hip_frame_read_dict(const void* d_frame, uint64_t avail, uint32_t n_bloc
 struct GatherScratch {
     uint64_t bitmap, wpre, misc, sel, in_off, out_off, skip, stored, crc, err, src_off, mask, codec, codec_bytes, blocks, total;
 };
-static GatherScratch gather_scratch(uint64_t n, uint64_t r, uint64_t m, uint32_t block_bits) {
+// with_codec = false leaves the decoder's scratch out (codec = 0, codec_bytes still says what it takes): an update
+// places one area for the decoder and the encoder behind its own pieces
+static GatherScratch gather_scratch(uint64_t n, uint64_t r, uint64_t m, uint32_t block_bits, bool with_codec = true) {
     GatherScratch G = {};
     uint64_t at = 0;
     auto take = [&at](uint64_t bytes) { const uint64_t v = at; at += align_up(bytes, 256); return v; };
@@ -2107,7 +2110,7 @@ static GatherScratch gather_scratch(uint64_t n, uint64_t r, uint64_t m, uint32_t
     G.src_off = take(r * 8 + 8);
     G.mask = take(r * 4 + 4);
     G.codec_bytes = sqz_hip_decode_scratch_bytes((uint32_t)(2 * m), m << block_bits);
-    G.codec = take(G.codec_bytes);
+    G.codec = with_codec ? take(G.codec_bytes) : 0;
     G.blocks = take((m << block_bits) + 16);
     G.total = at;
     return G;
@@ -2222,6 +2225,203 @@ int sqz_hip_frame_gather_dict(const void* d_frame, uint64_t avail, uint32_t n_bl
     return frame_gather_call(d_frame, avail, n_blocks, content_bytes, block_bits, d_offset, d_length, n_ranges,
                              max_length, max_blocks, d_dict, dict_bytes, d_out, out_capacity, d_out_off, d_range_err,
                              d_blocks_decoded, d_status, d_scratch, scratch_bytes, stream);
+}
+
+// ---- many ranges written into a resident frame in one call
+// where the pieces of an update's scratch lie (every piece 256-byte aligned): a gather's, a second offset per range,
+// and what the encode of the m slots and the merge take.  The encoder's scratch lies over the decoder's.
+struct UpdateScratch {
+    GatherScratch G;
+    uint64_t dst_off, enc_in_off, slab_off, out_bytes, enc_err, crc_new, seg_dst, seg_src, seg_len, verdict, dict_idx,
+             slabs, codec, codec_bytes, enc_codec_bytes, total;
+};
+static UpdateScratch update_scratch(uint64_t n, uint64_t r, uint64_t m, uint32_t block_bits, uint64_t dict_bytes) {
+    UpdateScratch U = {};
+    // a gather's pieces without its codec area: the larger of the decoder's and the encoder's goes at the end
+    U.G = gather_scratch(n, r, m, block_bits, false);
+    uint64_t at = U.G.total;
+    auto take = [&at](uint64_t bytes) { const uint64_t v = at; at += align_up(bytes, 256); return v; };
+    U.dst_off = take(r * 8 + 8);
+    U.enc_in_off = take((m + 1) * 8);
+    U.slab_off = take((m + 1) * 8);
+    U.out_bytes = take(m * 8 + 8);
+    U.enc_err = take(m * 4 + 4);
+    U.crc_new = take(m * 4 + 4);
+    U.seg_dst = take((2 * m + 2) * 8);
+    U.seg_src = take((2 * m + 1) * 8);
+    U.seg_len = take((2 * m + 1) * 8);
+    U.verdict = take(256);
+    U.dict_idx = take(dict_bytes != 0 ? dict_index_bytes(dict_bytes) : 0);
+    U.slabs = take(m * sqz_bound(1ull << block_bits));
+    U.enc_codec_bytes = sqz_hip_encode_scratch_bytes((uint32_t)m, m << block_bits);
+    U.codec_bytes = U.G.codec_bytes > U.enc_codec_bytes ? U.G.codec_bytes : U.enc_codec_bytes;
+    U.codec = take(U.codec_bytes);
+    U.total = at;
+    return U;
+}
+
+uint64_t sqz_hip_frame_update_scratch_bytes(uint32_t n_blocks, uint32_t n_ranges, uint32_t max_blocks, uint32_t block_bits,
+                                            uint64_t dict_bytes) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        dict_bytes > (uint64_t)sqzk_max_window - 1) { return 0; }
+    return update_scratch(n_blocks, n_ranges, max_blocks < n_blocks ? max_blocks : n_blocks, block_bits, dict_bytes).total;
+}
+
+static bool spans_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a_bytes != 0 && b_bytes != 0 && x < y + b_bytes && y < x + a_bytes;
+}
+
+// dict == NULL: versions 1 and 2 (sqz_hip_frame_update); else version 3
+static int frame_update_call(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                             uint32_t win_bits, uint32_t block_bits, const uint64_t* d_offset, const uint64_t* d_length,
+                             uint32_t n_ranges, uint64_t max_length, uint32_t max_blocks, const void* d_data,
+                             uint64_t data_bytes, uint64_t* d_data_off, uint32_t parse, const void* d_dict,
+                             uint64_t dict_bytes, void* d_new_frame, uint64_t capacity, uint64_t* d_frame_bytes,
+                             int32_t* d_range_err, uint32_t* d_blocks_encoded, int32_t* d_status, void* d_scratch,
+                             uint64_t scratch_bytes, void* stream) {
+    if (!frame_params_ok(win_bits, block_bits) || frame_blocks(content_bytes, block_bits) != n_blocks ||
+        !parse_ok(parse)) { return EINVAL; }
+    if (d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 || d_scratch == NULL || ((uintptr_t)d_scratch & 15u) != 0 ||
+        d_new_frame == NULL || ((uintptr_t)d_new_frame & 15u) != 0 || d_frame_bytes == NULL ||
+        d_status == NULL || d_blocks_encoded == NULL || d_data_off == NULL ||
+        (n_ranges > 0 && (d_offset == NULL || d_length == NULL || d_range_err == NULL)) ||
+        (data_bytes > 0 && d_data == NULL)) { return EINVAL; }
+    const uint32_t m = max_blocks < n_blocks ? max_blocks : n_blocks;
+    const UpdateScratch U = update_scratch(n_blocks, n_ranges, m, block_bits, d_dict != NULL ? dict_bytes : 0);
+    if (scratch_bytes < U.total) { return EINVAL; }
+    if (spans_overlap(d_new_frame, capacity, d_frame, avail) ||
+        spans_overlap(d_new_frame, capacity, d_scratch, scratch_bytes)) { return EINVAL; }
+    const uint64_t record = d_dict != NULL ? 8 : 0;
+    if (avail < 32 + 8 * (uint64_t)n_blocks + record) { return E2BIG; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    hipStream_t st = (hipStream_t)stream;
+    const GatherScratch& G = U.G;
+    const uint8_t* const frame = (const uint8_t*)d_frame;
+    uint8_t* const new_frame = (uint8_t*)d_new_frame;
+    uint8_t* const scratch = (uint8_t*)d_scratch;
+    uint32_t* bitmap = (uint32_t*)(scratch + G.bitmap);
+    uint32_t* wpre = (uint32_t*)(scratch + G.wpre);
+    uint64_t* idx_off = (uint64_t*)(scratch + G.misc);
+    uint32_t* idx_crc = (uint32_t*)(scratch + G.misc + 16);
+    uint64_t* spare = (uint64_t*)(scratch + G.misc + 32);
+    uint32_t* ctl = (uint32_t*)(scratch + G.misc + 160);      // [160,172): count, verdict, "win_bits is another"
+    uint32_t* sel = (uint32_t*)(scratch + G.sel);
+    uint64_t* in_off = (uint64_t*)(scratch + G.in_off);
+    uint64_t* out_off = (uint64_t*)(scratch + G.out_off);
+    uint32_t* skip = (uint32_t*)(scratch + G.skip);
+    uint32_t* stored = (uint32_t*)(scratch + G.stored);
+    uint32_t* crc = (uint32_t*)(scratch + G.crc);
+    int32_t* err = (int32_t*)(scratch + G.err);
+    uint64_t* src_off = (uint64_t*)(scratch + G.src_off);
+    uint32_t* mask = (uint32_t*)(scratch + G.mask);
+    uint8_t* slots = scratch + G.blocks;
+    uint64_t* dst_off = (uint64_t*)(scratch + U.dst_off);
+    uint64_t* enc_in_off = (uint64_t*)(scratch + U.enc_in_off);
+    uint64_t* slab_off = (uint64_t*)(scratch + U.slab_off);
+    uint64_t* out_bytes = (uint64_t*)(scratch + U.out_bytes);
+    int32_t* enc_err = (int32_t*)(scratch + U.enc_err);
+    uint32_t* crc_new = (uint32_t*)(scratch + U.crc_new);
+    uint64_t* seg_dst = (uint64_t*)(scratch + U.seg_dst);
+    uint64_t* seg_src = (uint64_t*)(scratch + U.seg_src);
+    uint64_t* seg_len = (uint64_t*)(scratch + U.seg_len);
+    uint32_t* flags = (uint32_t*)(scratch + U.verdict);
+    uint64_t* new_idx_off = (uint64_t*)(scratch + U.verdict + 16);
+    uint32_t* new_idx_crc = (uint32_t*)(scratch + U.verdict + 32);
+    uint8_t* slabs = scratch + U.slabs;
+    const uint64_t bb = 1ull << block_bits, slab = sqz_bound(bb);
+    // the covering blocks as a bitmap and a list, the data's layout, the patch's work list, the verdict on the request
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_gather_mark(d_offset, d_length, n_ranges, max_length, content_bytes, block_bits, n_blocks, bitmap, st);
+      sqzk::launch_gather_select(bitmap, n_blocks, d_offset, d_length, n_ranges, max_length, content_bytes, m,
+                                 data_bytes, wpre, sel, d_data_off, ctl, st);
+      sqzk::launch_update_plan(d_offset, d_length, n_ranges, max_length, content_bytes, block_bits, n_blocks, bitmap, wpre,
+                               d_data_off, d_range_err, src_off, dst_off, mask, frame, win_bits, flags, ctl, st); }
+    // the frame's checks and the touched blocks into their slots, as a gather's
+    const uint64_t idx_bytes = 8 * (uint64_t)n_blocks + record;
+    sqzk::launch_frame_plan(1, idx_bytes, idx_bytes, 0, idx_off, spare, st);
+    { SpanGuard g(st, SQZ_HIP_K_CRC32);
+      sqzk::launch_crc32_blocks(frame + 32, idx_off, 1, idx_crc, idx_bytes, st); }
+    DictDev dd;
+    uint32_t* dict_crc = nullptr;
+    if (d_dict != NULL) {
+        uint64_t* dict_off = (uint64_t*)(scratch + G.misc + 64);
+        dict_crc = (uint32_t*)(scratch + G.misc + 128);
+        sqzk::launch_frame_plan(1, dict_bytes, dict_bytes, 0, dict_off, dict_off + 4, st);
+        SpanGuard g(st, SQZ_HIP_K_CRC32);
+        sqzk::launch_crc32_blocks((const uint8_t*)d_dict, dict_off, 1, dict_crc, dict_bytes, st);
+        dd.bytes = (const uint8_t*)d_dict; dd.len = (uint32_t)dict_bytes;
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frame_open_list(frame, avail, n_blocks, content_bytes, idx_crc, (uint32_t)dict_bytes, dict_crc, bitmap,
+                                   wpre, sel, ctl, m, in_off, out_off, skip, stored, d_status, d_blocks_encoded, st,
+                                   block_bits); }
+    const bool work = m > 0 && n_ranges > 0;
+    if (work) {
+        uint32_t* counts = (uint32_t*)(scratch + U.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + U.codec + align_up((uint64_t)(2 * m) * 4, 256));
+        run_frame_decode(frame, in_off, out_off, 2 * m, bb, tokens, counts, slots, err, skip, stored, crc, dd, st, m);
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_update_verdict(frame, sel, ctl, m, err, crc, block_bits, content_bytes, slab, n_ranges, d_status,
+                                  d_blocks_encoded, mask, enc_in_off, slab_off, st); }
+    if (work) {
+        { SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);                // the patch: the data into the slots
+          if (max_length <= (uint64_t)sqzk_gather_copy_max) {
+              sqzk::launch_gather_copy((const uint8_t*)d_data, src_off, slots, dst_off, d_data_off, mask, n_ranges, st);
+          } else {
+              sqzk::launch_range_copy((const uint8_t*)d_data, src_off, slots, dst_off, d_data_off, mask, n_ranges, false,
+                                      max_length, st);
+          } }
+        { SpanGuard g(st, SQZ_HIP_K_CRC32);
+          sqzk::launch_crc32_blocks(slots, enc_in_off, m, crc_new, bb, st); }
+        if (d_dict != NULL) { dd = run_dict_index((const uint8_t*)d_dict, (uint32_t)dict_bytes, scratch + U.dict_idx, st); }
+        const uint64_t head = align_up((uint64_t)m * 4, 256);
+        const uint64_t slots_n = (U.enc_codec_bytes - head) / 8;
+        uint32_t* counts = (uint32_t*)(scratch + U.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + U.codec + head);
+        run_encode(d_dict != NULL ? 1 : finder_for(parse), slots, enc_in_off, m, 1u << win_bits, tokens, counts, tokens,
+                   tokens + slots_n, bb, slabs, slab_off, out_bytes, enc_err, 0, 0, slots_n, nullptr, st, parse,
+                   d_dict != NULL ? &dd : nullptr);
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frame_merge_index(frame, n_blocks, content_bytes, d_dict != NULL, bitmap, wpre, ctl, m, out_bytes, enc_err,
+                                     crc_new, slab, new_frame, capacity, seg_dst, seg_src, seg_len, new_idx_off,
+                                     d_frame_bytes, d_status, st); }
+    { SpanGuard g(st, SQZ_HIP_K_CRC32);
+      sqzk::launch_crc32_blocks(new_frame, new_idx_off, 1, new_idx_crc, idx_bytes, st); }
+    sqzk::launch_frame_seal(new_frame, new_idx_crc, n_blocks, d_status, st, (uint32_t)record);
+    { SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+      const uint64_t payload_off = frame_payload_off(n_blocks, record);
+      sqzk::launch_frame_splice(frame, slabs, slots, new_frame, seg_dst, seg_src, seg_len, m,
+                                capacity > payload_off ? capacity - payload_off : 0, st); }
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_frame_update(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                         uint32_t win_bits, uint32_t block_bits, const uint64_t* d_offset, const uint64_t* d_length,
+                         uint32_t n_ranges, uint64_t max_length, uint32_t max_blocks, const void* d_data,
+                         uint64_t data_bytes, uint64_t* d_data_off, uint32_t parse, void* d_new_frame, uint64_t capacity,
+                         uint64_t* d_frame_bytes, int32_t* d_range_err, uint32_t* d_blocks_encoded, int32_t* d_status,
+                         void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return frame_update_call(d_frame, avail, n_blocks, content_bytes, win_bits, block_bits, d_offset, d_length, n_ranges,
+                             max_length, max_blocks, d_data, data_bytes, d_data_off, parse, NULL, 0, d_new_frame, capacity,
+                             d_frame_bytes, d_range_err, d_blocks_encoded, d_status, d_scratch, scratch_bytes, stream);
+}
+
+int sqz_hip_frame_update_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                              uint32_t win_bits, uint32_t block_bits, const uint64_t* d_offset, const uint64_t* d_length,
+                              uint32_t n_ranges, uint64_t max_length, uint32_t max_blocks, const void* d_data,
+                              uint64_t data_bytes, uint64_t* d_data_off, uint32_t parse, const void* d_dict,
+                              uint64_t dict_bytes, void* d_new_frame, uint64_t capacity, uint64_t* d_frame_bytes,
+                              int32_t* d_range_err, uint32_t* d_blocks_encoded, int32_t* d_status, void* d_scratch,
+                              uint64_t scratch_bytes, void* stream) {
+    if (win_bits > (uint32_t)sqz_max_win_bits || !dict_ok(d_dict, dict_bytes, 1u << win_bits)) { return EINVAL; }
+    return frame_update_call(d_frame, avail, n_blocks, content_bytes, win_bits, block_bits, d_offset, d_length, n_ranges,
+                             max_length, max_blocks, d_data, data_bytes, d_data_off, parse, d_dict, dict_bytes, d_new_frame,
+                             capacity, d_frame_bytes, d_range_err, d_blocks_encoded, d_status, d_scratch, scratch_bytes,
+                             stream);
 }
 
 int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t* d_crc, void* stream) {

@@ -127,8 +127,9 @@ __device__ __forceinline__ uint64_t block_len(uint64_t b, uint64_t bb, uint64_t 
     return at >= content_bytes ? 0 : (content_bytes - at < bb ? content_bytes - at : bb);
 }
 // the writer's rule: a block whose stream is not smaller than its content is stored, padded to 8 bytes
+__device__ __forceinline__ bool block_stored(uint64_t stream_bytes, uint64_t len) { return stream_bytes >= len; }
 __device__ __forceinline__ uint64_t payload_share(uint64_t stream_bytes, uint64_t len) {
-    return stream_bytes >= len ? (len + 7) & ~(uint64_t)7 : stream_bytes;
+    return block_stored(stream_bytes, len) ? (len + 7) & ~(uint64_t)7 : stream_bytes;
 }
 
 __device__ __forceinline__ uint32_t load_le32(const uint8_t* p) {
@@ -346,7 +347,7 @@ void frame_index_body(const uint64_t* __restrict__ out_bytes, const int32_t* __r
     for (uint64_t b = b0; b < b1; b++) {
         const uint64_t v = out_bytes[b];
         const uint64_t len = block_len(b, bb, content_bytes);
-        const bool st = store && v >= len;
+        const bool st = store && block_stored(v, len);
         const uint64_t share = store ? payload_share(v, len) : v;
         dense_off[b] = ok ? at : 0;
         copy_bytes[b] = ok && !st ? v : 0;
@@ -1097,6 +1098,441 @@ void launch_gather_copy(const uint8_t* src, const uint64_t* src_off, uint8_t* ds
     const uint64_t per = kCopyThreads / kGatherLanes;
     hipLaunchKernelGGL(gather_copy_kernel, dim3((unsigned)(((uint64_t)n_ranges + per - 1) / per)), dim3(kCopyThreads),
                        0, stream, src, src_off, dst, dst_off, len_off, mask, n_ranges);
+}
+
+// ---------------------------------------------------------------------------------------- update
+// Many byte ranges WRITTEN into a resident frame in one call ("Update"): the distinct covering
+// blocks are decoded into slots as a gather decodes them, patched, checksummed and encoded again, every other stream
+// is carried over as it lies.  mark -> select -> update_plan -> update_caps -> open for a list -> the decode chain ->
+// update_verdict -> the patch (either range copy) -> crc32 -> the encoder over the slots -> frame_merge_index -> crc32
+// and seal of the new index -> frame_splice.
+constexpr int kErrERANGE = 34, kErrENODATA = 61;   // <errno.h>, checked in abi.hip
+
+// One lane per range, before the frame is opened (validity needs the ranges alone): range_err[r] = EINVAL or 0, and
+// the range's entry in the patch copy's work list -- from data + data_off[r] (len_off = data_off: an invalid range
+// has length 0 there) to its place in the slots: its covering blocks are consecutive slots, so it lies in one piece
+// at (slot of its first block << block_bits) + offset mod 2^block_bits.  flags[0] (zero at the start) becomes 1 when
+// any range is invalid.
+__global__ __launch_bounds__(kGatherThreads)
+void update_plan_kernel(const uint64_t* __restrict__ offset, const uint64_t* __restrict__ length, uint32_t n_ranges,
+                        uint64_t max_length, uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks,
+                        const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ wpre,
+                        const uint64_t* __restrict__ data_off, int32_t* __restrict__ range_err,
+                        uint64_t* __restrict__ src_off, uint64_t* __restrict__ dst_off, uint32_t* __restrict__ mask,
+                        uint32_t* __restrict__ flags) {
+    const uint64_t r = (uint64_t)blockIdx.x * kGatherThreads + threadIdx.x;
+    if (r >= n_ranges) { return; }
+    const uint64_t off = offset[r], len = length[r];
+    if (!gather_range_ok(off, len, max_length, content_bytes)) {
+        range_err[r] = kErrEINVAL; src_off[r] = 0; dst_off[r] = 0; mask[r] = 0;
+        flags[0] = 1u;                             // every writer writes the same word
+        return;
+    }
+    uint64_t at = 0;
+    const uint64_t first = off >> block_bits;
+    if (len > 0 && first < n_blocks) {
+        const uint32_t w = bitmap[first >> 5], bit = (uint32_t)first & 31u;
+        const uint64_t k0 = wpre[first >> 5] + (uint32_t)__builtin_popcount(w & ((1u << bit) - 1u));
+        at = (k0 << block_bits) + (off & ((1ull << block_bits) - 1));
+    }
+    range_err[r] = 0;
+    src_off[r] = data_off[r];
+    dst_off[r] = at;
+    mask[r] = len > 0 ? 1u : 0u;
+}
+
+// One lane: what the open kernel takes as the verdict on the request, in the call's order.  ctl[1] arrives as
+// gather_select_kernel left it (ENOBUFS, or ENOSPC with the data's size as the capacity) and leaves as EINVAL for a
+// frame whose win_bits is not the caller's (ctl[2] = 1: the frame's own status, no block counted), else ERANGE, else
+// ENOBUFS, else ENODATA, else 0.
+__global__ __launch_bounds__(64)
+void update_caps_kernel(const uint8_t* __restrict__ frame, uint32_t win_bits, const uint32_t* __restrict__ flags,
+                        uint32_t* __restrict__ ctl) {
+    if (threadIdx.x != 0) { return; }
+    const uint32_t c = ctl[1];
+    const bool other = frame[5] != win_bits;
+    ctl[1] = other ? (uint32_t)kErrEINVAL : flags[0] != 0 ? (uint32_t)kErrERANGE
+             : c == (uint32_t)kErrENOBUFS ? c : c != 0 ? (uint32_t)kErrENODATA : 0u;
+    ctl[2] = other ? 1u : 0u;
+}
+
+// One workgroup, once the touched blocks lie decoded in their slots (entry 2k of err and crc is slot k's): *status
+// stays what the open kernel said, else becomes the first non-zero errno among the touched blocks in ascending order --
+// the decoder's, or EILSEQ where the bytes are not the ones the index entry's CRC-32 was taken of.  With any status
+// everything behind is switched off: mask[] of the patch copy is cleared and the encoder's blocks are empty.  Else
+// enc_in_off[k] = k << block_bits for the slots in use, the end of the last one (the only one that can be the ragged
+// last block) behind them.  slab_off[k] = k * slab_bytes either way (m + 1 entries each).
+__global__ __launch_bounds__(256)
+void update_verdict_kernel(const uint8_t* __restrict__ frame, const uint32_t* __restrict__ sel,
+                           const uint32_t* __restrict__ ctl, uint32_t max_blocks, const int32_t* __restrict__ err,
+                           const uint32_t* __restrict__ crc, uint32_t block_bits, uint64_t content_bytes,
+                           uint64_t slab_bytes, uint32_t n_ranges, int32_t* __restrict__ status,
+                           uint32_t* __restrict__ blocks_encoded, uint32_t* __restrict__ mask,
+                           uint64_t* __restrict__ enc_in_off, uint64_t* __restrict__ slab_off) {
+    __shared__ uint32_t first_bad[256];
+    __shared__ int32_t verdict;
+    const uint32_t t = threadIdx.x;
+    const uint32_t count = *status == 0 ? ctl[0] : 0u;         // (<= max_blocks: the verdict on the cap was 0)
+    const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
+    uint32_t mine = 0xFFFFFFFFu;
+    for (uint64_t k = t; k < count; k += 256) {
+        if (err[2 * k] != 0 || crc[2 * k] != index[2 * (uint64_t)sel[k] + 1]) { mine = (uint32_t)k; break; }
+    }
+    first_bad[t] = mine;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t bad = 0xFFFFFFFFu;
+        for (int k = 0; k < 256; k++) { bad = first_bad[k] < bad ? first_bad[k] : bad; }
+        int32_t st = *status;
+        if (st == 0 && bad != 0xFFFFFFFFu) { st = err[2 * (uint64_t)bad] != 0 ? err[2 * (uint64_t)bad] : kErrEILSEQ; }
+        *status = st;
+        if (ctl[2] != 0) { *blocks_encoded = 0u; }
+        verdict = st;
+    }
+    __syncthreads();
+    const bool ok = verdict == 0;
+    const uint64_t bb = 1ull << block_bits;
+    const uint64_t end = ok && count > 0 ? (uint64_t)(count - 1) * bb + block_len(sel[count - 1], bb, content_bytes) : 0;
+    for (uint64_t k = t; k <= max_blocks; k += 256) {
+        enc_in_off[k] = !ok ? 0 : k < count ? k * bb : end;
+        slab_off[k] = k * slab_bytes;
+    }
+    if (!ok) {
+        for (uint64_t r = t; r < n_ranges; r += 256) { mask[r] = 0u; }
+    }
+}
+
+void launch_update_plan(const uint64_t* offset, const uint64_t* length, uint32_t n_ranges, uint64_t max_length,
+                        uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks, const uint32_t* bitmap,
+                        const uint32_t* wpre, const uint64_t* data_off, int32_t* range_err, uint64_t* src_off,
+                        uint64_t* dst_off, uint32_t* mask, const uint8_t* frame, uint32_t win_bits, uint32_t* flags,
+                        uint32_t* ctl, hipStream_t stream) {
+#ifdef SQZ_WAVE_EMU
+    flags[0] = 0u;
+#else
+    (void)hipMemsetAsync(flags, 0, 4, stream);
+#endif
+    if (n_ranges > 0) {
+        const uint64_t grid = ((uint64_t)n_ranges + kGatherThreads - 1) / kGatherThreads;
+        hipLaunchKernelGGL(update_plan_kernel, dim3((unsigned)grid), dim3(kGatherThreads), 0, stream, offset, length,
+                           n_ranges, max_length, content_bytes, block_bits, n_blocks, bitmap, wpre, data_off, range_err,
+                           src_off, dst_off, mask, flags);
+    }
+    hipLaunchKernelGGL(update_caps_kernel, dim3(1), dim3(64), 0, stream, frame, win_bits, flags, ctl);
+}
+
+void launch_update_verdict(const uint8_t* frame, const uint32_t* sel, const uint32_t* ctl, uint32_t max_blocks,
+                           const int32_t* err, const uint32_t* crc, uint32_t block_bits, uint64_t content_bytes,
+                           uint64_t slab_bytes, uint32_t n_ranges, int32_t* status, uint32_t* blocks_encoded,
+                           uint32_t* mask, uint64_t* enc_in_off, uint64_t* slab_off, hipStream_t stream) {
+    hipLaunchKernelGGL(update_verdict_kernel, dim3(1), dim3(256), 0, stream, frame, sel, ctl, max_blocks, err, crc,
+                       block_bits, content_bytes, slab_bytes, n_ranges, status, blocks_encoded, mask, enc_in_off, slab_off);
+}
+
+// where a segment of the new payload comes from: bits 62..63 of its seg_src word, the offset below them
+constexpr uint64_t kSegOld = 0, kSegSlab = 1ull << 62, kSegSlot = 2ull << 62, kSegOffMask = (1ull << 62) - 1;
+
+// One workgroup, the scans shaped as in frame_index_body: the index of the new frame merged from the old entries and
+// the encoder's results.  Block b is touched iff its bit is set in bitmap; its slot k (wpre, as in the open kernel) has
+// its new stream in slab k (out_bytes[k], enc_err[k]) and its patched content's CRC-32 in crc_new[k]; in a frame whose
+// version stores blocks it is stored by frame_index_body's rule (block_stored).  A kept block keeps its entry.  Both
+// the old and the new shares are scanned, which gives every block its place in either payload.
+// *status arrives as update_verdict_kernel left it.  Non-zero: *frame_bytes_out = 0, idx_off = {0, 0}, an empty segment
+// table, nothing else.  Else the first encoder errno in ascending order (or EINVAL for a size no entry holds), else
+// E2BIG when the new frame does not fit capacity (*frame_bytes_out = what it takes) -- again nothing of the frame is
+// written and the table is empty.  Else header (the old one's fields, the new payload_bytes, index_crc left to
+// frame_seal_kernel), index, the old record (kDict) and the padding, idx_off = the index's range for its checksum, and
+// the segment table of frame_splice_kernel for the count = ctl[0] touched blocks:
+//     segment 2k      the kept streams in front of touched block sel[k] (behind sel[k - 1]), from the old frame
+//     segment 2k + 1  block sel[k]: its slab, or its slot when it is stored (seg_len = its content's bytes; the share
+//                     is that rounded up to 8)
+//     segment 2 count the kept streams behind the last touched block; segments up to 2 max_blocks are empty.
+// seg_dst (2 max_blocks + 2 entries, ascending): where a segment starts in the new frame -- the next entry is its end;
+// seg_src, seg_len (2 max_blocks + 1): its source (kSeg*) and how many source bytes there are (all ones: as many as
+// the segment takes).  A kept run's old offset is the old scan at its first block: no array of n_blocks words.
+template <bool kDict>
+__device__ __forceinline__
+void frame_merge_index_body(const uint8_t* __restrict__ old, uint32_t n_blocks, uint64_t content_bytes,
+                            const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ wpre,
+                            const uint32_t* __restrict__ ctl, uint32_t max_blocks,
+                            const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ enc_err,
+                            const uint32_t* __restrict__ crc_new, uint64_t slab_bytes, uint8_t* __restrict__ frame,
+                            uint64_t capacity, uint64_t* __restrict__ seg_dst, uint64_t* __restrict__ seg_src,
+                            uint64_t* __restrict__ seg_len, uint64_t* __restrict__ idx_off,
+                            uint64_t* __restrict__ frame_bytes_out, int32_t* __restrict__ status) {
+    __shared__ uint64_t sums_old[256];
+    __shared__ uint64_t sums_new[256];
+    __shared__ int32_t first_err[256];
+    __shared__ int32_t verdict;
+    __shared__ uint64_t new_end;
+    const uint32_t t = threadIdx.x;
+    const uint64_t segments = 2 * (uint64_t)max_blocks + 1;
+    const uint64_t record = kDict ? 8 : 0;
+    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + record + 15) & ~(uint64_t)15;
+    if (*status != 0) {                            // (uniform: every lane reads the same word)
+        for (uint64_t j = t; j <= segments; j += 256) {
+            seg_dst[j] = 0;
+            if (j < segments) { seg_src[j] = 0; seg_len[j] = 0; }
+        }
+        if (t == 0) { *frame_bytes_out = 0; idx_off[0] = 0; idx_off[1] = 0; }
+        return;
+    }
+    // the open kernel has passed this header: its fields are in range
+    const uint32_t* const old_index = reinterpret_cast<const uint32_t*>(old + 32);
+    const uint32_t block_bits = old[6];
+    const bool bit31 = kDict || old[4] == 2;                       // an entry's bit 31 is the stored bit
+    const bool store = kDict ? (old[7] & kFrameStored) != 0 : old[4] == 2;
+    const uint32_t words_mask = bit31 ? ~kStoredBit : 0xFFFFFFFFu;
+    const uint64_t most_words = bit31 ? 0x7FFFFFFFull : 0xFFFFFFFFull;
+    const uint64_t bb = 1ull << block_bits;
+    const uint32_t count = ctl[0];
+    const uint64_t per = ((uint64_t)n_blocks + 255) / 256;
+    const uint64_t b0 = t * per < n_blocks ? t * per : n_blocks;
+    const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+    uint64_t sum_old = 0, sum_new = 0;
+    int32_t bad = 0;
+    for (uint64_t b = b0; b < b1; b++) {
+        const uint64_t share_old = (uint64_t)(old_index[2 * b] & words_mask) * 8;
+        uint64_t share_new = share_old;
+        const uint32_t w = bitmap[b >> 5], bit = (uint32_t)b & 31u;
+        if (((w >> bit) & 1u) != 0) {
+            const uint64_t k = wpre[b >> 5] + (uint32_t)__builtin_popcount(w & ((1u << bit) - 1u));
+            const uint64_t v = out_bytes[k];
+            if (bad == 0 && enc_err[k] != 0) { bad = enc_err[k]; }
+            if (bad == 0 && ((v & 7u) != 0 || (v >> 3) > most_words)) { bad = kErrEINVAL; }
+            share_new = store ? payload_share(v, block_len(b, bb, content_bytes)) : v;
+        }
+        sum_old += share_old;
+        sum_new += share_new;
+    }
+    sums_old[t] = sum_old;
+    sums_new[t] = sum_new;
+    first_err[t] = bad;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t run_old = 0, run_new = 0;
+        int32_t st = 0;
+        for (int k = 0; k < 256; k++) {
+            const uint64_t vo = sums_old[k], vn = sums_new[k];
+            sums_old[k] = run_old; sums_new[k] = run_new;
+            run_old += vo; run_new += vn;
+            if (st == 0) { st = first_err[k]; }
+        }
+        const uint64_t frame_bytes = payload_off + run_new;
+        if (st == 0 && frame_bytes > capacity) { st = kErrE2BIG; }
+        verdict = st;
+        new_end = frame_bytes;
+        *status = st;
+        *frame_bytes_out = st == 0 || st == kErrE2BIG ? frame_bytes : 0;
+        idx_off[0] = st == 0 ? 32 : 0;
+        idx_off[1] = st == 0 ? 32 + 8 * (uint64_t)n_blocks + record : 0;
+        if (st == 0) {
+            const uint32_t* const oh = reinterpret_cast<const uint32_t*>(old);
+            uint32_t* const h = reinterpret_cast<uint32_t*>(frame);
+            h[0] = oh[0]; h[1] = oh[1];                            // magic; version, win_bits, block_bits, flags
+            h[2] = (uint32_t)content_bytes; h[3] = (uint32_t)(content_bytes >> 32);
+            h[4] = (uint32_t)run_new; h[5] = (uint32_t)(run_new >> 32);
+            h[6] = n_blocks;
+            h[7] = 0u;                                             // index_crc: frame_seal_kernel
+            const uint32_t* const old_behind = oh + 8 + 2 * (uint64_t)n_blocks;
+            uint32_t* const behind = h + 8 + 2 * (uint64_t)n_blocks;
+            if (kDict) {
+                behind[0] = old_behind[0]; behind[1] = old_behind[1];
+                if ((n_blocks & 1u) == 0) { behind[2] = 0u; behind[3] = 0u; }
+            } else if ((n_blocks & 1u) != 0) { behind[0] = 0u; behind[1] = 0u; }
+            seg_dst[0] = payload_off; seg_src[0] = kSegOld | payload_off; seg_len[0] = ~(uint64_t)0;
+        }
+    }
+    __syncthreads();
+    if (verdict != 0) {
+        for (uint64_t j = t; j <= segments; j += 256) {
+            seg_dst[j] = 0;
+            if (j < segments) { seg_src[j] = 0; seg_len[j] = 0; }
+        }
+        return;
+    }
+    uint32_t* const index = reinterpret_cast<uint32_t*>(frame + 32);
+    uint64_t at_old = payload_off + sums_old[t], at_new = payload_off + sums_new[t];
+    for (uint64_t b = b0; b < b1; b++) {
+        const uint32_t e = old_index[2 * b];
+        const uint64_t share_old = (uint64_t)(e & words_mask) * 8;
+        uint64_t share_new = share_old;
+        const uint32_t w = bitmap[b >> 5], bit = (uint32_t)b & 31u;
+        if (((w >> bit) & 1u) != 0) {
+            const uint64_t k = wpre[b >> 5] + (uint32_t)__builtin_popcount(w & ((1u << bit) - 1u));
+            const uint64_t v = out_bytes[k];
+            const uint64_t len = block_len(b, bb, content_bytes);
+            const bool st = store && block_stored(v, len);
+            share_new = store ? payload_share(v, len) : v;
+            index[2 * b] = (uint32_t)(share_new >> 3) | (st ? kStoredBit : 0u);
+            index[2 * b + 1] = crc_new[k];
+            seg_dst[2 * k + 1] = at_new;
+            seg_src[2 * k + 1] = st ? kSegSlot | (k * bb) : kSegSlab | (k * slab_bytes);
+            seg_len[2 * k + 1] = st ? len : share_new;
+            seg_dst[2 * k + 2] = at_new + share_new;               // the kept run behind it: the old frame's bytes
+            seg_src[2 * k + 2] = kSegOld | (at_old + share_old);
+            seg_len[2 * k + 2] = ~(uint64_t)0;
+        } else {
+            index[2 * b] = e;
+            index[2 * b + 1] = old_index[2 * b + 1];
+        }
+        at_old += share_old;
+        at_new += share_new;
+    }
+    // the end of the last kept run, and the empty segments behind the count
+    for (uint64_t j = 2 * (uint64_t)count + 1 + t; j <= segments; j += 256) {
+        seg_dst[j] = new_end;
+        if (j < segments) { seg_src[j] = 0; seg_len[j] = 0; }
+    }
+}
+
+__global__ __launch_bounds__(256)
+void frame_merge_index_kernel(const uint8_t* __restrict__ old, uint32_t n_blocks, uint64_t content_bytes,
+                              const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ wpre,
+                              const uint32_t* __restrict__ ctl, uint32_t max_blocks,
+                              const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ enc_err,
+                              const uint32_t* __restrict__ crc_new, uint64_t slab_bytes, uint8_t* __restrict__ frame,
+                              uint64_t capacity, uint64_t* __restrict__ seg_dst, uint64_t* __restrict__ seg_src,
+                              uint64_t* __restrict__ seg_len, uint64_t* __restrict__ idx_off,
+                              uint64_t* __restrict__ frame_bytes_out, int32_t* __restrict__ status) {
+    frame_merge_index_body<false>(old, n_blocks, content_bytes, bitmap, wpre, ctl, max_blocks, out_bytes, enc_err, crc_new,
+                                  slab_bytes, frame, capacity, seg_dst, seg_src, seg_len, idx_off, frame_bytes_out, status);
+}
+
+__global__ __launch_bounds__(256)
+void frame_merge_index_v3_kernel(const uint8_t* __restrict__ old, uint32_t n_blocks, uint64_t content_bytes,
+                                 const uint32_t* __restrict__ bitmap, const uint32_t* __restrict__ wpre,
+                                 const uint32_t* __restrict__ ctl, uint32_t max_blocks,
+                                 const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ enc_err,
+                                 const uint32_t* __restrict__ crc_new, uint64_t slab_bytes, uint8_t* __restrict__ frame,
+                                 uint64_t capacity, uint64_t* __restrict__ seg_dst, uint64_t* __restrict__ seg_src,
+                                 uint64_t* __restrict__ seg_len, uint64_t* __restrict__ idx_off,
+                                 uint64_t* __restrict__ frame_bytes_out, int32_t* __restrict__ status) {
+    frame_merge_index_body<true>(old, n_blocks, content_bytes, bitmap, wpre, ctl, max_blocks, out_bytes, enc_err, crc_new,
+                                 slab_bytes, frame, capacity, seg_dst, seg_src, seg_len, idx_off, frame_bytes_out, status);
+}
+
+void launch_frame_merge_index(const uint8_t* old, uint32_t n_blocks, uint64_t content_bytes, bool dict,
+                              const uint32_t* bitmap, const uint32_t* wpre, const uint32_t* ctl, uint32_t max_blocks,
+                              const uint64_t* out_bytes, const int32_t* enc_err, const uint32_t* crc_new,
+                              uint64_t slab_bytes, uint8_t* frame, uint64_t capacity, uint64_t* seg_dst, uint64_t* seg_src,
+                              uint64_t* seg_len, uint64_t* idx_off, uint64_t* frame_bytes_out, int32_t* status,
+                              hipStream_t stream) {
+    if (dict) {
+        hipLaunchKernelGGL(frame_merge_index_v3_kernel, dim3(1), dim3(256), 0, stream, old, n_blocks, content_bytes, bitmap,
+                           wpre, ctl, max_blocks, out_bytes, enc_err, crc_new, slab_bytes, frame, capacity, seg_dst, seg_src,
+                           seg_len, idx_off, frame_bytes_out, status);
+    } else {
+        hipLaunchKernelGGL(frame_merge_index_kernel, dim3(1), dim3(256), 0, stream, old, n_blocks, content_bytes, bitmap,
+                           wpre, ctl, max_blocks, out_bytes, enc_err, crc_new, slab_bytes, frame, capacity, seg_dst, seg_src,
+                           seg_len, idx_off, frame_bytes_out, status);
+    }
+}
+
+// The payload of the new frame in one pass, partitioned by DESTINATION: a workgroup takes kSpliceChunk bytes of it
+// (grid-stride behind the launch's workgroups), finds the first segment that reaches into its chunk by bisection of
+// seg_dst and copies the segments' intersections with the chunk until the chunk ends.  A 500 MB kept run between a few
+// thousand touched blocks is shared by as many workgroups as it has chunks; range_copy_kernel over the runs would give
+// every run the same few.  Every segment starts and ends on a multiple of 8 bytes in the destination, its source
+// offset is one as well, the payload starts on a multiple of 16 and so does every chunk: a destination row of 16 bytes
+// lies in one chunk and in at most two segments.  A row inside a segment is one aligned 16-byte store of one aligned
+// 16-byte load (both sides agree mod 16) or of two aligned 8-byte loads joined (they differ by 8: both halves are the
+// segment's own, so nothing outside a source is read).  A row whose halves belong to two segments is written once, by the segment that
+// holds its lower half, which fetches the upper half from the next segment that is not empty; only where the payload
+// itself ends in mid-row is a store 8 bytes.  Source bytes a segment does not have (seg_len: a stored ragged last
+// block's padding) are zeros.  Nothing outside [seg_dst[0], seg_dst[segments]) is written.
+constexpr uint64_t kSpliceChunk = 32768;
+constexpr unsigned kSpliceMaxGroups = 2048;
+
+// 8 source bytes at p (8-byte aligned) of which only the first `have` exist: the others are zeros
+__device__ __forceinline__ uint64_t splice_load8(const uint8_t* p, uint64_t have) {
+    if (have >= 8) { return *reinterpret_cast<const uint64_t*>(p); }
+    uint64_t v = 0;
+    for (uint32_t j = 0; j < have; j++) { v |= (uint64_t)p[j] << (8 * j); }
+    return v;
+}
+
+struct SpliceSource { const uint8_t* from; uint64_t have; };       // a segment's first source byte, and how many there are
+
+__device__ __forceinline__ SpliceSource splice_source(const uint8_t* old, const uint8_t* slabs, const uint8_t* slots,
+                                                      uint64_t word, uint64_t len, uint64_t room) {
+    const uint64_t sel = word & ~kSegOffMask;
+    SpliceSource s;
+    s.from = (sel == kSegOld ? old : sel == kSegSlab ? slabs : slots) + (word & kSegOffMask);
+    s.have = len < room ? len : room;
+    return s;
+}
+
+__global__ __launch_bounds__(kCopyThreads)
+void frame_splice_kernel(const uint8_t* __restrict__ old, const uint8_t* __restrict__ slabs,
+                         const uint8_t* __restrict__ slots, uint8_t* __restrict__ dst,
+                         const uint64_t* __restrict__ seg_dst, const uint64_t* __restrict__ seg_src,
+                         const uint64_t* __restrict__ seg_len, uint32_t segments) {
+    const uint64_t base = seg_dst[0], end = seg_dst[segments];
+    if (end <= base) { return; }
+    const uint64_t chunks = (end - base + kSpliceChunk - 1) / kSpliceChunk;
+    const uint32_t tid = threadIdx.x;
+    for (uint64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const uint64_t c0 = base + c * kSpliceChunk;
+        const uint64_t c1 = end - c0 > kSpliceChunk ? c0 + kSpliceChunk : end;
+        uint32_t lo = 0, hi = segments - 1;                        // the first segment that ends behind c0
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (seg_dst[mid + 1] > c0) { hi = mid; } else { lo = mid + 1; }
+        }
+        for (uint32_t j = lo; j < segments; j++) {
+            const uint64_t s0 = seg_dst[j], s1 = seg_dst[j + 1];
+            if (s0 >= c1) { break; }
+            if (s1 <= s0) { continue; }
+            const uint64_t a = s0 > c0 ? s0 : c0, b = s1 < c1 ? s1 : c1;
+            const SpliceSource src = splice_source(old, slabs, slots, seg_src[j], seg_len[j], s1 - s0);
+            for (uint64_t r = (a & ~(uint64_t)15) + 16 * (uint64_t)tid; r < b; r += 16 * (uint64_t)kCopyThreads) {
+                if (r < a) { continue; }                           // the lower half is the segment's in front: its row
+                const uint8_t* const sp = src.from + (r - s0);
+                const uint64_t have = src.have > r - s0 ? src.have - (r - s0) : 0;
+                if (r + 16 <= b) {
+                    uint4 v;
+                    if (have >= 16 && ((uintptr_t)sp & 15u) == 0) {
+                        v = *reinterpret_cast<const uint4*>(sp);
+                    } else if (have >= 16) {                       // sp is 8 mod 16: two aligned halves, both the segment's
+                        const uint64_t q0 = *reinterpret_cast<const uint64_t*>(sp);
+                        const uint64_t q1 = *reinterpret_cast<const uint64_t*>(sp + 8);
+                        v.x = (uint32_t)q0; v.y = (uint32_t)(q0 >> 32); v.z = (uint32_t)q1; v.w = (uint32_t)(q1 >> 32);
+                    } else {
+                        const uint64_t q0 = splice_load8(sp, have), q1 = splice_load8(sp + 8, have > 8 ? have - 8 : 0);
+                        v.x = (uint32_t)q0; v.y = (uint32_t)(q0 >> 32); v.z = (uint32_t)q1; v.w = (uint32_t)(q1 >> 32);
+                    }
+                    *reinterpret_cast<uint4*>(dst + r) = v;
+                    continue;
+                }
+                // the segment ends in mid-row (never the chunk, unless the payload does): the upper half is the first
+                // 8 bytes of the next segment that is not empty
+                const uint64_t q0 = splice_load8(sp, have);
+                uint32_t n = j + 1;
+                while (n < segments && seg_dst[n + 1] <= seg_dst[n]) { n++; }
+                if (n < segments) {
+                    const SpliceSource nx = splice_source(old, slabs, slots, seg_src[n], seg_len[n], seg_dst[n + 1] - seg_dst[n]);
+                    const uint64_t q1 = splice_load8(nx.from, nx.have);
+                    uint4 v;
+                    v.x = (uint32_t)q0; v.y = (uint32_t)(q0 >> 32); v.z = (uint32_t)q1; v.w = (uint32_t)(q1 >> 32);
+                    *reinterpret_cast<uint4*>(dst + r) = v;
+                } else {
+                    *reinterpret_cast<uint64_t*>(dst + r) = q0;
+                }
+            }
+        }
+    }
+}
+
+// most_bytes: the most the new payload can be (the launch's size; the table on the device says what it is)
+void launch_frame_splice(const uint8_t* old, const uint8_t* slabs, const uint8_t* slots, uint8_t* dst,
+                         const uint64_t* seg_dst, const uint64_t* seg_src, const uint64_t* seg_len, uint32_t max_blocks,
+                         uint64_t most_bytes, hipStream_t stream) {
+    uint64_t groups = (most_bytes + kSpliceChunk - 1) / kSpliceChunk;
+    if (groups > kSpliceMaxGroups) { groups = kSpliceMaxGroups; }
+    if (groups < 1) { groups = 1; }
+    hipLaunchKernelGGL(frame_splice_kernel, dim3((unsigned)groups), dim3(kCopyThreads), 0, stream, old, slabs, slots, dst,
+                       seg_dst, seg_src, seg_len, 2 * max_blocks + 1);
 }
 
 } // namespace sqzk

@@ -179,4 +179,37 @@ void launch_gather_plan(const uint8_t* frame, const uint64_t* offset, const uint
 void launch_gather_copy(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, const uint64_t* dst_off,
                         const uint64_t* len_off, const uint32_t* mask, uint32_t n_ranges, hipStream_t stream);
 
+// many ranges WRITTEN into a resident frame in one call (frame.hip, "update"): mark and select as
+// for a gather (select's out_off is the data's layout, its capacity the data's size), then
+// plan: range_err (EINVAL / 0) and the patch copy's work list (src_off into the data, dst_off into the slots, mask;
+//   len_off = data_off), flags[0] = any range invalid; then ctl[1] = the verdict on the request in the call's order
+//   (EINVAL for a frame whose win_bits is another, with ctl[2] = 1; ERANGE; ENOBUFS; ENODATA) for launch_frame_open_list.
+//   ctl: 3 words here.
+// verdict: after the decode chain; *status = the open's, else the first failed touched block's errno; with any status
+//   mask[] is cleared and enc_in_off (max_blocks + 1 entries) is all zeros, else enc_in_off[k] = k << block_bits up to
+//   the count and the end of the last slot behind it; slab_off[k] = k * slab_bytes.
+// merge_index: the new frame's header, index, record and padding from the old entries and the encoder's results
+//   (out_bytes, enc_err, crc_new: max_blocks entries by slot), *frame_bytes_out, *status (the encoder's errno, E2BIG),
+//   idx_off for the index checksum, and the segment table: seg_dst 2 max_blocks + 2 entries, seg_src / seg_len
+//   2 max_blocks + 1.  dict: a version-3 frame (the record is carried over).
+// splice: the new payload from the table's three sources; most_bytes sizes the launch.
+void launch_update_plan(const uint64_t* offset, const uint64_t* length, uint32_t n_ranges, uint64_t max_length,
+                        uint64_t content_bytes, uint32_t block_bits, uint32_t n_blocks, const uint32_t* bitmap,
+                        const uint32_t* wpre, const uint64_t* data_off, int32_t* range_err, uint64_t* src_off,
+                        uint64_t* dst_off, uint32_t* mask, const uint8_t* frame, uint32_t win_bits, uint32_t* flags,
+                        uint32_t* ctl, hipStream_t stream);
+void launch_update_verdict(const uint8_t* frame, const uint32_t* sel, const uint32_t* ctl, uint32_t max_blocks,
+                           const int32_t* err, const uint32_t* crc, uint32_t block_bits, uint64_t content_bytes,
+                           uint64_t slab_bytes, uint32_t n_ranges, int32_t* status, uint32_t* blocks_encoded,
+                           uint32_t* mask, uint64_t* enc_in_off, uint64_t* slab_off, hipStream_t stream);
+void launch_frame_merge_index(const uint8_t* old, uint32_t n_blocks, uint64_t content_bytes, bool dict,
+                              const uint32_t* bitmap, const uint32_t* wpre, const uint32_t* ctl, uint32_t max_blocks,
+                              const uint64_t* out_bytes, const int32_t* enc_err, const uint32_t* crc_new,
+                              uint64_t slab_bytes, uint8_t* frame, uint64_t capacity, uint64_t* seg_dst, uint64_t* seg_src,
+                              uint64_t* seg_len, uint64_t* idx_off, uint64_t* frame_bytes_out, int32_t* status,
+                              hipStream_t stream);
+void launch_frame_splice(const uint8_t* old, const uint8_t* slabs, const uint8_t* slots, uint8_t* dst,
+                         const uint64_t* seg_dst, const uint64_t* seg_src, const uint64_t* seg_len, uint32_t max_blocks,
+                         uint64_t most_bytes, hipStream_t stream);
+
 } // namespace sqzk

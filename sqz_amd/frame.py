@@ -327,16 +327,17 @@ def read_frame(d_frame, offset: int, length: int, d_out=None, info: dict = None,
     return d_out[:length], err[:covering], status
 
 
-def _ranges_dev(values, device, what):
-    """a list of offsets or lengths as a uint64 device tensor's bits: (tensor, host list or None)"""
+def _ranges_dev(values, device, what, who="gather_frame"):
+    """a list of offsets or lengths as a uint64 device tensor's bits: (tensor, host list or None); `who` names the
+    caller in the errors"""
     import torch
     if isinstance(values, torch.Tensor):
         if values.dim() != 1 or values.dtype not in (torch.int64, torch.uint64):
-            raise ValueError(f"gather_frame: {what} must be a one-dimensional int64 or uint64 tensor")
+            raise ValueError(f"{who}: {what} must be a one-dimensional int64 or uint64 tensor")
         return values.contiguous().to(device), None
     host = [int(v) for v in values]
     if any(v < 0 or v >> 64 for v in host):
-        raise ValueError(f"gather_frame: {what} must be 0 .. 2^64 - 1")
+        raise ValueError(f"{who}: {what} must be 0 .. 2^64 - 1")
     signed = [v - (1 << 64) if v >> 63 else v for v in host]
     return torch.tensor(signed, dtype=torch.int64, device=device), host
 
@@ -400,6 +401,77 @@ def gather_frame(d_frame, offsets, lengths, max_length: int = None, max_blocks: 
     else:
         _raise(L.sqz_hip_frame_gather(*head, *tail), "sqz_hip_frame_gather")
     return d_out, out_off, range_err[:count], blocks_decoded, status
+
+
+def update_frame(d_frame, offsets, lengths, data, max_length: int = None, max_blocks: int = None, d_out=None,
+                 info: dict = None, dictionary=None, parse="greedy", scratch=None):
+    """Many byte ranges written into a device-resident frame in one call: the new frame, in d_out (uint8, of the
+    version's bound when not given; it must not overlap d_frame), is the frame of the content with data's bytes at
+    content[offsets[r] : offsets[r] + lengths[r]] for every r -- byte for byte the encoder's frame of that content with
+    the same parse.  Only the distinct covering blocks are decoded, verified, patched and encoded again; every other
+    stream is carried over as it lies.  data: the ranges' bytes packed in request order, bytes-like or a uint8 device
+    tensor.  offsets / lengths, max_length, max_blocks, `info` and dictionary as for gather_frame (sequences are checked
+    here, ValueError; device tensors go through unread, and max_length is then required).  Where ranges overlap each
+    overlapped byte is one of the candidates'.
+    Enqueues and returns (d_out, frame_bytes int64[1], data_off int64[n + 1], range_err int32[n], blocks_encoded
+    int32[1], status int32[1]), all device tensors: d_out[:frame_bytes] is the new frame when status is 0 after a
+    synchronise, and d_out is untouched otherwise.  status: the frame's own; ERANGE when the device finds a range invalid
+    (range_err EINVAL there); ENOBUFS (blocks_encoded says what max_blocks takes); ENODATA when data is shorter than the
+    ranges; a touched block's decode or checksum error; E2BIG when d_out is too small (frame_bytes says what it takes)."""
+    import torch
+    L = N.lib()
+    parse = parse_code(parse)
+    if info is None:
+        info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    n, content, bits = info["n_blocks"], info["content_bytes"], info["block_bytes"].bit_length() - 1
+    device = d_frame.device
+    d = _dict_dev(dictionary, 1 << info["win_bits"], device) if dictionary is not None else None
+    d_offsets, h_offsets = _ranges_dev(offsets, device, "offsets", "update_frame")
+    d_lengths, h_lengths = _ranges_dev(lengths, device, "lengths", "update_frame")
+    count = d_offsets.numel()
+    if d_lengths.numel() != count:
+        raise ValueError("update_frame: as many lengths as offsets")
+    if max_length is None:
+        if h_lengths is None:
+            raise ValueError("update_frame: max_length is required when the lengths are a device tensor")
+        max_length = max(h_lengths, default=0)
+    if h_offsets is not None and h_lengths is not None:
+        for o, ln in zip(h_offsets, h_lengths):
+            if ln > max_length or o > content or ln > content - o:
+                raise ValueError(f"update_frame: range ({o}, {ln}) is longer than max_length or leaves the content")
+    if isinstance(data, torch.Tensor):
+        if data.dtype != torch.uint8 or data.dim() != 1:
+            raise ValueError("update_frame: data tensor must be one-dimensional uint8")
+        d_data = data.contiguous().to(device)
+    else:
+        d_data = torch.frombuffer(bytearray(bytes(data) or b"\0"), dtype=torch.uint8)[:len(data)].to(device)
+    if max_blocks is None:
+        max_blocks = gather_bound(n, count, max_length, bits)
+    if d_out is None:
+        if info["version"] == 3:                             # with or without stored blocks: the larger bound
+            bound = max(L.sqz_frame_bound_dict(content, bits, FRAME_DICT), L.sqz_frame_bound_dict(content, bits, FRAME_DICT | FRAME_STORED))
+        elif info["version"] == 2:
+            bound = L.sqz_frame_bound_ex(content, bits, FRAME_STORED)
+        else:
+            bound = L.sqz_frame_bound(content, bits)
+        d_out = torch.empty(max(int(bound), 1), dtype=torch.uint8, device=device)
+    frame_bytes = torch.zeros(1, dtype=torch.int64, device=device)
+    data_off = torch.zeros(count + 1, dtype=torch.int64, device=device)
+    range_err = torch.zeros(max(count, 1), dtype=torch.int32, device=device)
+    blocks_encoded = torch.zeros(1, dtype=torch.int32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    if scratch is None:
+        scratch = _scratch_for(device, int(L.sqz_hip_frame_update_scratch_bytes(n, count, max_blocks, bits,
+                                                                                  d.numel() if d is not None else 0)))
+    head = (_ptr(d_frame), d_frame.numel(), n, content, info["win_bits"], bits, _ptr(d_offsets), _ptr(d_lengths), count,
+            max_length, max_blocks, _ptr(d_data) if d_data.numel() else None, d_data.numel(), _ptr(data_off), parse)
+    tail = (_ptr(d_out), d_out.numel(), _ptr(frame_bytes), _ptr(range_err), _ptr(blocks_encoded), _ptr(status),
+            _ptr(scratch), scratch.numel(), _stream())
+    if d is not None:
+        _raise(L.sqz_hip_frame_update_dict(*head, _ptr(d), d.numel(), *tail), "sqz_hip_frame_update_dict")
+    else:
+        _raise(L.sqz_hip_frame_update(*head, *tail), "sqz_hip_frame_update")
+    return d_out, frame_bytes, data_off, range_err[:count], blocks_encoded, status
 
 
 # ---- file tool ----------------------------------------------------------------------------------
