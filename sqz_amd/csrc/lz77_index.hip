@@ -34,6 +34,7 @@
 //                       walks that merge with the real path instead of one serial walk.
 #include "sqz_device.h"
 #include "sqz_kernels.h"
+#include "sort_bases.h"
 
 namespace sqzk {
 
@@ -45,7 +46,8 @@ constexpr int kSortWaves = kSortThreads / kWave;
 constexpr int kSortTile = 4 * kSortThreads;      // elements per workgroup tile (4 rows of 64 per wave)
 
 // The three digit histograms do not depend on the order of the elements (a position's key
-// bytes are fixed), so one sweep over the stream's BYTES gives all three; each pass is then a
+// bytes are fixed), so one sweep over the stream's BYTES gives all three (it counts the digit of
+// pass 0; the other two histograms are sums of bins of that one: sort_bases.h); each pass is then a
 // single sweep over the elements.  The scatter does not write elements where they fall: every
 // 4096-element tile is first ordered by digit in LDS (stable: wave order, then row and lane order
 // inside a wave), then copied out, so a digit's elements of one tile leave as one contiguous run.
@@ -312,23 +314,23 @@ void index_sort_kernel(const uint8_t* __restrict__ in,
     const bool carry = bytes <= (1u << 24);                   // (8 + 8 + 8) byte 0 fits above the position
     // pass p sorts by key bits [shift[p], shift[p] + width[p])
     const int w0 = small ? 10 : 8, w1 = small ? 7 : 8, w2 = small ? 7 : 8;
-    const int s1 = w0, s2 = w0 + w1;
-    const uint32_t m0 = (1u << w0) - 1u, m1 = (1u << w1) - 1u;
+    const uint32_t m0 = (1u << w0) - 1u;
     SortSec sec;
 #ifdef SQZ_STATS
     sec.last = __builtin_readcyclecounter();
     const uint64_t sec_begin = sec.last;
 #endif
     // ---- all three histograms from the bytes ------------------------------------------------
-    for (int d = tid; d < 3 * kSortBins; d += kSortThreads) { (&lds.gbase[0][0])[d] = 0; }
+    // The sweep counts pass 0's digit only.  The digits of passes 1 and 2 are coarser functions of the same bytes one and
+    // two positions earlier, so their histograms are sums of bins of pass 0's, put right at the block's two ends by its
+    // first two and last two bytes (sort_bases.h) -- one LDS atomic per position instead of three, and the two that are
+    // gone are the ones whose lanes met on few addresses (7-bit digits of Zipf bytes).
+    const SortEnds ends = {src[0], src[1], src[bytes - 2], src[bytes - 1]};
+    for (int d = tid; d < kSortBins; d += kSortThreads) { lds.gbase[0][d] = 0; }
     __syncthreads();
     // a thread takes four neighbouring positions from two dwords, the next two already in flight; the few positions
     // after the last whole quad (its 7 bytes must exist) go one by one
-    auto count_key = [&](uint32_t key) {
-        atomicAdd(&lds.gbase[0][key & m0], 1u);
-        atomicAdd(&lds.gbase[1][(key >> s1) & m1], 1u);
-        atomicAdd(&lds.gbase[2][key >> s2], 1u);
-    };
+    auto count_key = [&](uint32_t key) { atomicAdd(&lds.gbase[0][key & m0], 1u); };
     const uint32_t quads = bytes >= 8 ? (uint32_t)((bytes - 8) / 4) + 1u : 0u;
     if ((uint32_t)tid < quads) {
         uint32_t lo = load_u32_unaligned(src + 4u * (uint32_t)tid), hi = load_u32_unaligned(src + 4u * (uint32_t)tid + 4u);
@@ -341,6 +343,8 @@ void index_sort_kernel(const uint8_t* __restrict__ in,
         }
     }
     for (uint32_t k = 4u * quads + (uint32_t)tid; k < count; k += (uint32_t)kSortThreads) { count_key(sort_key(src, bytes, k)); }
+    __syncthreads();
+    sort_bases_derive(lds.gbase[0], lds.gbase[1], lds.gbase[2], small, ends, tid, kSortThreads);
     __syncthreads();
     if (wave < 3) {                                        // exclusive scans: counts -> bases
         uint32_t* const g = lds.gbase[wave];
