@@ -763,6 +763,79 @@ SQZ_API int sqz_hip_frame_update_dict(const void* d_frame, uint64_t avail, uint3
                                       uint32_t* d_blocks_encoded, int32_t* d_status, void* d_scratch,
                                       uint64_t scratch_bytes, void* stream);
 
+/* More content BEHIND a resident frame in one call: the new frame is the frame of content || data.  The conventions
+ * are the update's (device pointers; d_frame, d_new_frame and d_scratch 16-byte aligned; asynchronous, no host
+ * synchronisation inside; n_blocks, content_bytes, win_bits and block_bits from a host copy of the header).
+ * sqz_hip_frame_append is for versions 1 and 2, _append_dict for version 3.  There is no format change: the result is an
+ * ordinary frame of the old one's version, and every reader takes it as it is.
+ *
+ * With C = content_bytes, A = data_bytes, b = block_bits: t = C mod 2^b is the number of bytes in a ragged last block,
+ * keep = n_blocks - (t > 0 && A > 0 ? 1 : 0), m = ceil((t + A) / 2^b) for A > 0 (t counted only when t > 0) and 0 for
+ * A == 0, and n' = keep + m.  The host knows all of these: no device count sizes a launch.
+ *
+ * The call writes a NEW frame into d_new_frame (at most `capacity` bytes, *d_frame_bytes its size); the old one is only
+ * read and the two may not overlap.  The new frame keeps the old version, win_bits, block_bits and flags, and in
+ * version 3 the dictionary's record; content_bytes = C + A, payload_bytes, n_blocks = n' and index_crc are new, and
+ * payload_off is pad16(32 + 8 n' (+ 8)).  Blocks 0 .. keep - 1 are KEPT: their index entries and streams are copied as
+ * they are, neither decoded nor verified -- a damaged kept block stays damaged and is still reported by a later
+ * decode.  If t > 0 and A > 0 the old last block is TOUCHED: it is decoded into the head of a staging area in the
+ * scratch (a stored block and a version-3 block with the dictionary as well) and verified against its CRC-32, and the
+ * data follows it directly.  The m blocks of tail || data are checksummed, encoded (parse: SQZ_PARSE_GREEDY or
+ * SQZ_PARSE_LAZY; with the dictionary in version 3) and, in a frame of version 2 or of version 3 with SQZ_FRAME_STORED,
+ * stored when their stream is not smaller than their content (the writer's rule).  If t == 0 nothing is decoded.  On
+ * status 0 the new frame is byte for byte what the encoder of that version writes for content || data with the same
+ * parse, provided the kept streams were written with that parse too.
+ * A == 0 writes a copy of the old frame (its exact bytes), or its status: nothing is decoded and nothing is encoded.
+ * C == 0 is an empty frame (32 bytes, 48 with a dictionary's record): the result is the encoder's frame of the data.
+ *
+ * *d_status is the first of these that applies, and with ANY non-zero status not one byte of d_new_frame is written:
+ *   1. the frame's own status: the checks of sqz_hip_frame_gather / _gather_dict in their order (the index checksum and
+ *      the dictionary's length and CRC-32, EILSEQ, among them), then EINVAL for a frame whose win_bits is not the
+ *      argument.  *d_blocks_encoded = 0.
+ *   2. the touched block's errno: the decoder's, or EILSEQ for a checksum that does not hold.  The call does not build
+ *      on content it cannot verify.
+ *   3. the first encoder errno among the m blocks in ascending order, or EINVAL for a size that no index entry holds.
+ *   4. E2BIG: the new frame does not fit capacity; *d_frame_bytes is the size it takes.
+ *   *d_frame_bytes is the frame's size for status 0 and for 4, and 0 for 1 to 3.  *d_blocks_encoded is m in every case
+ *   but 1.  A capacity of sqz_frame_bound / _bound_ex / _bound_dict of C + A for the frame's version is always enough.
+ * EINVAL at the call, nothing enqueued: win_bits outside 10..15 or block_bits outside 12..24; n_blocks !=
+ *   ceil(content_bytes / 2^block_bits); a null or misaligned d_frame, d_new_frame or d_scratch; a null d_frame_bytes,
+ *   d_status or d_blocks_encoded; data_bytes > 0 with a null d_data; C + A overflowing, or a content that the frame
+ *   bound answers 0 for; n' (or the m + 1 segments of the new payload) not fitting 32 bits; [d_new_frame, + capacity)
+ *   overlapping [d_frame, + avail), the data or the scratch; the data overlapping the scratch; a scratch smaller than
+ *   the function says; a parse that is none; _dict: d_dict == NULL or dict_bytes outside 1 .. 2^win_bits - 1.  E2BIG
+ *   when avail does not cover header and index (and record), ENODEV without a device (after the argument checks).
+ * Scratch, with t and m as above, w = ceil(n_blocks / 32), D = dict_bytes (0 for versions 1 and 2), every term rounded
+ * up to 256:
+ *       sqz_hip_frame_append_scratch_bytes(n_blocks, C, A, b, D) =
+ *           2 * (4 w + 4) + 256 + 8 + 2 * 24 + 4 * 12               [the open for a list of one block: bitmap and its
+ *                                                                     prefix counts, control words, the list, two
+ *                                                                     offsets and four masks and results for its slot]
+ *           + (t + A + 16)                                          [the staging area; t only when the block is touched,
+ *                                                                     16 alone for A == 0]
+ *           + 2 * 8 (m + 1) + (8 m + 8) + 2 * (4 m + 4)             [the encoder's two offset lists, its sizes, errnos
+ *                                                                     and the new checksums]
+ *           + 8 (m + 2) + 2 * 8 (m + 1)                             [the segment table of m + 1 segments]
+ *           + 256 + (D > 0 ? 256 + 2 * round_up_256(4 * (D + 64)) : 0)  [the verdict words, the dictionary's index]
+ *           + m * sqz_bound(2^b)                                    [m slabs]
+ *           + max(sqz_hip_decode_scratch_bytes(2, 2^b), sqz_hip_encode_scratch_bytes(m, m << b))
+ *   (the encoder's scratch over the decoder's, which is done by then); 0 for a bad block_bits, D > 32767, or sizes that
+ *   wrap.  The encoder's 8 bytes per input byte and the slabs' 2 make a 1 GiB append take about 11 GiB of scratch: a
+ *   caller with less memory appends in pieces -- appends compose, two of them leave the frame of one append of the
+ *   concatenation.                                                                                                    */
+SQZ_API uint64_t sqz_hip_frame_append_scratch_bytes(uint32_t n_blocks, uint64_t content_bytes, uint64_t data_bytes,
+                                                    uint32_t block_bits, uint64_t dict_bytes);
+SQZ_API int sqz_hip_frame_append(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                 uint32_t win_bits, uint32_t block_bits, const void* d_data, uint64_t data_bytes,
+                                 uint32_t parse, void* d_new_frame, uint64_t capacity, uint64_t* d_frame_bytes,
+                                 uint32_t* d_blocks_encoded, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                 void* stream);
+SQZ_API int sqz_hip_frame_append_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                      uint32_t win_bits, uint32_t block_bits, const void* d_data, uint64_t data_bytes,
+                                      uint32_t parse, const void* d_dict, uint64_t dict_bytes, void* d_new_frame,
+                                      uint64_t capacity, uint64_t* d_frame_bytes, uint32_t* d_blocks_encoded,
+                                      int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* Live timing of the last kernels enqueued through this library on the
  * calling thread's context, measured with HIP events ON THE LAUNCH STREAM.
  * Enabled with sqz_hip_set_timing(1); values in milliseconds.               */
@@ -779,7 +852,7 @@ enum {
     SQZ_HIP_K_RC_ENCODE = 7,      /* rc_encode_kernel  } R-era range coder            */
     SQZ_HIP_K_RC_DECODE = 8,      /* rc_decode_kernel  } (include/sqz/sqz_rc.h)       */
     SQZ_HIP_K_CRC32 = 9,          /* crc32_blocks_kernel } SQZF frames                */
-    SQZ_HIP_K_FRAME_INDEX = 10,   /* frame_index_kernel / frame_open_kernel } (and an update's planning) */
+    SQZ_HIP_K_FRAME_INDEX = 10,   /* frame_index_kernel / frame_open_kernel } (and an update's or append's planning) */
     SQZ_HIP_K_RANGE_COPY = 11,    /* range_copy_kernel: stored blocks (SQZF version 2); frame_splice_kernel */
     SQZ_HIP_KERNELS = 12
 };

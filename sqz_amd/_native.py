@@ -192,6 +192,12 @@ PROTOTYPES = {
     "sqz_hip_frame_update_dict": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp,
                                             C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint32, _vp,
                                             C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_frame_append_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64]),
+    "sqz_hip_frame_append": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                       C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_frame_append_dict": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp,
+                                            C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp,
+                                            C.c_uint64, _vp]),
     "sqz_hip_set_finder": (None, [C.c_int]),
     "sqz_hip_get_finder": (C.c_int, []),
     "sqz_hip_set_timing": (None, [C.c_int]),

@@ -2424,6 +2424,211 @@ int sqz_hip_frame_update_dict(const void* d_frame, uint64_t avail, uint32_t n_bl
                              stream);
 }
 
+// ---- more content behind a resident frame in one call
+// What the host works out for an append from the header's copy: t, the bytes of a ragged last block; whether that block
+// is touched; keep, the blocks carried over; m, the blocks to encode; stage = t + data_bytes (t = 0 unless touched).
+struct AppendShape { uint64_t tail, keep, m, n_new, stage; bool touched, ok; };
+static AppendShape append_shape(uint64_t n_blocks, uint64_t content_bytes, uint64_t data_bytes, uint32_t block_bits) {
+    AppendShape S = {};
+    const uint64_t bb = 1ull << block_bits;
+    S.tail = content_bytes & (bb - 1);
+    S.touched = n_blocks > 0 && S.tail != 0 && data_bytes > 0;
+    S.keep = n_blocks - (S.touched ? 1 : 0);
+    const uint64_t head = S.touched ? S.tail : 0;
+    S.ok = data_bytes <= ~content_bytes && data_bytes <= ~(uint64_t)0 - 2 * bb;     // C + A and t + A + 2^b without a wrap
+    if (!S.ok) { return S; }
+    S.stage = data_bytes > 0 ? head + data_bytes : 0;
+    S.m = (S.stage + bb - 1) >> block_bits;
+    S.n_new = S.keep + S.m;
+    S.ok = S.n_new <= 0xFFFFFFFFull && S.m < 0xFFFFFFFFull;      // n' and the m + 1 segments in 32 bits
+    return S;
+}
+
+// where the pieces of an append's scratch lie (every piece 256-byte aligned): the open for a list of one block, the
+// staging area, what the encode of the m blocks and the new index take.  The encoder's scratch lies over the decoder's.
+struct AppendScratch {
+    uint64_t bitmap, wpre, misc, sel, in_off, out_off, skip, stored, crc, err, staging, enc_in_off, slab_off, out_bytes,
+             enc_err, crc_new, seg_dst, seg_src, seg_len, verdict, dict_idx, slabs, codec, codec_bytes, enc_codec_bytes, total;
+};
+static AppendScratch append_scratch(uint64_t n, const AppendShape& S, uint32_t block_bits, uint64_t dict_bytes) {
+    AppendScratch P = {};
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) { const uint64_t v = at; at += align_up(bytes, 256); return v; };
+    const uint64_t words = (n + 31) / 32, m = S.m, bb = 1ull << block_bits;
+    P.bitmap = take(words * 4 + 4);
+    P.wpre = take(words * 4 + 4);
+    P.misc = take(256);                 // as a gather's: [160,168) count and verdict on the request
+    P.sel = take(8);
+    P.in_off = take(3 * 8);             // one slot, two entries (frame_open_body<.., true>)
+    P.out_off = take(3 * 8);
+    P.skip = take(2 * 4 + 4);
+    P.stored = take(2 * 4 + 4);
+    P.crc = take(2 * 4 + 4);
+    P.err = take(2 * 4 + 4);
+    P.staging = take(S.stage + 16);
+    P.enc_in_off = take((m + 1) * 8);
+    P.slab_off = take((m + 1) * 8);
+    P.out_bytes = take(m * 8 + 8);
+    P.enc_err = take(m * 4 + 4);
+    P.crc_new = take(m * 4 + 4);
+    P.seg_dst = take((m + 2) * 8);
+    P.seg_src = take((m + 1) * 8);
+    P.seg_len = take((m + 1) * 8);
+    P.verdict = take(256);
+    P.dict_idx = take(dict_bytes != 0 ? dict_index_bytes(dict_bytes) : 0);
+    P.slabs = take(m * sqz_bound(bb));
+    P.enc_codec_bytes = sqz_hip_encode_scratch_bytes((uint32_t)m, m << block_bits);
+    const uint64_t dec = sqz_hip_decode_scratch_bytes(2, bb);
+    P.codec_bytes = dec > P.enc_codec_bytes ? dec : P.enc_codec_bytes;
+    P.codec = take(P.codec_bytes);
+    P.total = at;
+    return P;
+}
+
+uint64_t sqz_hip_frame_append_scratch_bytes(uint32_t n_blocks, uint64_t content_bytes, uint64_t data_bytes,
+                                            uint32_t block_bits, uint64_t dict_bytes) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        dict_bytes > (uint64_t)sqzk_max_window - 1) { return 0; }
+    const AppendShape S = append_shape(n_blocks, content_bytes, data_bytes, block_bits);
+    if (!S.ok) { return 0; }
+    return append_scratch(n_blocks, S, block_bits, dict_bytes).total;
+}
+
+// dict == NULL: versions 1 and 2 (sqz_hip_frame_append); else version 3
+static int frame_append_call(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                             uint32_t win_bits, uint32_t block_bits, const void* d_data, uint64_t data_bytes,
+                             uint32_t parse, const void* d_dict, uint64_t dict_bytes, void* d_new_frame,
+                             uint64_t capacity, uint64_t* d_frame_bytes, uint32_t* d_blocks_encoded, int32_t* d_status,
+                             void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!frame_params_ok(win_bits, block_bits) || frame_blocks(content_bytes, block_bits) != n_blocks ||
+        !parse_ok(parse)) { return EINVAL; }
+    if (d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 || d_scratch == NULL || ((uintptr_t)d_scratch & 15u) != 0 ||
+        d_new_frame == NULL || ((uintptr_t)d_new_frame & 15u) != 0 || d_frame_bytes == NULL ||
+        d_status == NULL || d_blocks_encoded == NULL || (data_bytes > 0 && d_data == NULL)) { return EINVAL; }
+    const AppendShape S = append_shape(n_blocks, content_bytes, data_bytes, block_bits);
+    if (!S.ok || sqz_frame_bound(content_bytes + data_bytes, block_bits) == 0) { return EINVAL; }
+    const AppendScratch P = append_scratch(n_blocks, S, block_bits, d_dict != NULL ? dict_bytes : 0);
+    if (scratch_bytes < P.total) { return EINVAL; }
+    if (spans_overlap(d_new_frame, capacity, d_frame, avail) || spans_overlap(d_new_frame, capacity, d_data, data_bytes) ||
+        spans_overlap(d_new_frame, capacity, d_scratch, scratch_bytes) ||
+        spans_overlap(d_data, data_bytes, d_scratch, scratch_bytes)) { return EINVAL; }
+    const uint64_t record = d_dict != NULL ? 8 : 0;
+    if (avail < 32 + 8 * (uint64_t)n_blocks + record) { return E2BIG; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* const frame = (const uint8_t*)d_frame;
+    uint8_t* const new_frame = (uint8_t*)d_new_frame;
+    uint8_t* const scratch = (uint8_t*)d_scratch;
+    uint32_t* bitmap = (uint32_t*)(scratch + P.bitmap);
+    uint32_t* wpre = (uint32_t*)(scratch + P.wpre);
+    uint64_t* idx_off = (uint64_t*)(scratch + P.misc);
+    uint32_t* idx_crc = (uint32_t*)(scratch + P.misc + 16);
+    uint64_t* spare = (uint64_t*)(scratch + P.misc + 32);
+    uint32_t* ctl = (uint32_t*)(scratch + P.misc + 160);      // [160,168): count, verdict on the request
+    uint32_t* sel = (uint32_t*)(scratch + P.sel);
+    uint64_t* in_off = (uint64_t*)(scratch + P.in_off);
+    uint64_t* out_off = (uint64_t*)(scratch + P.out_off);
+    uint32_t* skip = (uint32_t*)(scratch + P.skip);
+    uint32_t* stored = (uint32_t*)(scratch + P.stored);
+    uint32_t* crc = (uint32_t*)(scratch + P.crc);
+    int32_t* err = (int32_t*)(scratch + P.err);
+    uint8_t* staging = scratch + P.staging;
+    uint64_t* enc_in_off = (uint64_t*)(scratch + P.enc_in_off);
+    uint64_t* slab_off = (uint64_t*)(scratch + P.slab_off);
+    uint64_t* out_bytes = (uint64_t*)(scratch + P.out_bytes);
+    int32_t* enc_err = (int32_t*)(scratch + P.enc_err);
+    uint32_t* crc_new = (uint32_t*)(scratch + P.crc_new);
+    uint64_t* seg_dst = (uint64_t*)(scratch + P.seg_dst);
+    uint64_t* seg_src = (uint64_t*)(scratch + P.seg_src);
+    uint64_t* seg_len = (uint64_t*)(scratch + P.seg_len);
+    uint64_t* new_idx_off = (uint64_t*)(scratch + P.verdict + 16);       // the verdict words: [16,32) the new index's
+    uint32_t* new_idx_crc = (uint32_t*)(scratch + P.verdict + 32);       // range, [32,36) its checksum, [64,104) the
+    uint64_t* copy = (uint64_t*)(scratch + P.verdict + 64);              // staging copy's work list
+    uint8_t* slabs = scratch + P.slabs;
+    const uint64_t bb = 1ull << block_bits, slab = sqz_bound(bb);
+    const uint32_t m = (uint32_t)S.m, n_new = (uint32_t)S.n_new;
+    // the last block as a list of one, if it is touched, and the verdict on the request
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_append_plan(frame, n_blocks, content_bytes, data_bytes, block_bits, win_bits, bitmap, wpre, sel, ctl, st); }
+    // the frame's checks and the touched block to the head of the staging area, as a gather's into its slot
+    const uint64_t idx_bytes = 8 * (uint64_t)n_blocks + record;
+    sqzk::launch_frame_plan(1, idx_bytes, idx_bytes, 0, idx_off, spare, st);
+    { SpanGuard g(st, SQZ_HIP_K_CRC32);
+      sqzk::launch_crc32_blocks(frame + 32, idx_off, 1, idx_crc, idx_bytes, st); }
+    DictDev dd;
+    uint32_t* dict_crc = nullptr;
+    if (d_dict != NULL) {
+        uint64_t* dict_off = (uint64_t*)(scratch + P.misc + 64);
+        dict_crc = (uint32_t*)(scratch + P.misc + 128);
+        sqzk::launch_frame_plan(1, dict_bytes, dict_bytes, 0, dict_off, dict_off + 4, st);
+        SpanGuard g(st, SQZ_HIP_K_CRC32);
+        sqzk::launch_crc32_blocks((const uint8_t*)d_dict, dict_off, 1, dict_crc, dict_bytes, st);
+        dd.bytes = (const uint8_t*)d_dict; dd.len = (uint32_t)dict_bytes;
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frame_open_list(frame, avail, n_blocks, content_bytes, idx_crc, (uint32_t)dict_bytes, dict_crc, bitmap,
+                                   wpre, sel, ctl, 1, in_off, out_off, skip, stored, d_status, d_blocks_encoded, st,
+                                   block_bits); }
+    if (S.touched) {
+        uint32_t* counts = (uint32_t*)(scratch + P.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + P.codec + 256);
+        run_frame_decode(frame, in_off, out_off, 2, bb, tokens, counts, staging, err, skip, stored, crc, dd, st, 1);
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_append_verdict(frame, n_blocks, ctl, err, crc, block_bits, content_bytes, data_bytes, m, slab, d_status,
+                                  d_blocks_encoded, copy, enc_in_off, slab_off, st); }
+    if (m > 0) {
+        { SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);                // the data behind the touched block's bytes
+          sqzk::launch_range_copy((const uint8_t*)d_data, copy, staging, copy + 1, copy + 2, (const uint32_t*)(copy + 4), 1,
+                                  false, data_bytes, st); }
+        { SpanGuard g(st, SQZ_HIP_K_CRC32);
+          sqzk::launch_crc32_blocks(staging, enc_in_off, m, crc_new, bb, st); }
+        if (d_dict != NULL) { dd = run_dict_index((const uint8_t*)d_dict, (uint32_t)dict_bytes, scratch + P.dict_idx, st); }
+        const uint64_t head = align_up((uint64_t)m * 4, 256);
+        const uint64_t slots_n = (P.enc_codec_bytes - head) / 8;
+        uint32_t* counts = (uint32_t*)(scratch + P.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + P.codec + head);
+        run_encode(d_dict != NULL ? 1 : finder_for(parse), staging, enc_in_off, m, 1u << win_bits, tokens, counts, tokens,
+                   tokens + slots_n, bb, slabs, slab_off, out_bytes, enc_err, 0, 0, slots_n, nullptr, st, parse,
+                   d_dict != NULL ? &dd : nullptr);
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frame_append_index(frame, n_blocks, content_bytes, data_bytes, m, d_dict != NULL, out_bytes, enc_err,
+                                      crc_new, slab, new_frame, capacity, seg_dst, seg_src, seg_len, new_idx_off,
+                                      d_frame_bytes, d_status, st); }
+    const uint64_t new_idx_bytes = 8 * (uint64_t)n_new + record;
+    { SpanGuard g(st, SQZ_HIP_K_CRC32);
+      sqzk::launch_crc32_blocks(new_frame, new_idx_off, 1, new_idx_crc, new_idx_bytes, st); }
+    sqzk::launch_frame_seal(new_frame, new_idx_crc, n_new, d_status, st, (uint32_t)record);
+    { SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+      const uint64_t payload_off = frame_payload_off(n_new, record);
+      sqzk::launch_frame_splice_segments(frame, slabs, staging, new_frame, seg_dst, seg_src, seg_len, m + 1,
+                                         capacity > payload_off ? capacity - payload_off : 0, st); }
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_frame_append(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                         uint32_t win_bits, uint32_t block_bits, const void* d_data, uint64_t data_bytes,
+                         uint32_t parse, void* d_new_frame, uint64_t capacity, uint64_t* d_frame_bytes,
+                         uint32_t* d_blocks_encoded, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                         void* stream) {
+    return frame_append_call(d_frame, avail, n_blocks, content_bytes, win_bits, block_bits, d_data, data_bytes, parse,
+                             NULL, 0, d_new_frame, capacity, d_frame_bytes, d_blocks_encoded, d_status, d_scratch,
+                             scratch_bytes, stream);
+}
+
+int sqz_hip_frame_append_dict(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                              uint32_t win_bits, uint32_t block_bits, const void* d_data, uint64_t data_bytes,
+                              uint32_t parse, const void* d_dict, uint64_t dict_bytes, void* d_new_frame,
+                              uint64_t capacity, uint64_t* d_frame_bytes, uint32_t* d_blocks_encoded, int32_t* d_status,
+                              void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (win_bits > (uint32_t)sqz_max_win_bits || !dict_ok(d_dict, dict_bytes, 1u << win_bits)) { return EINVAL; }
+    return frame_append_call(d_frame, avail, n_blocks, content_bytes, win_bits, block_bits, d_data, data_bytes, parse,
+                             d_dict, dict_bytes, d_new_frame, capacity, d_frame_bytes, d_blocks_encoded, d_status,
+                             d_scratch, scratch_bytes, stream);
+}
+
 int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t* d_crc, void* stream) {
     if (n == 0) { return 0; }
     if (d_in == NULL || d_in_off == NULL || d_crc == NULL) { return EINVAL; }

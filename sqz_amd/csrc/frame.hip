@@ -1535,4 +1535,289 @@ void launch_frame_splice(const uint8_t* old, const uint8_t* slabs, const uint8_t
                        seg_dst, seg_src, seg_len, 2 * max_blocks + 1);
 }
 
+// the same kernel over a table of `segments` segments (an append's: one kept run and its new blocks)
+void launch_frame_splice_segments(const uint8_t* old, const uint8_t* slabs, const uint8_t* slots, uint8_t* dst,
+                                  const uint64_t* seg_dst, const uint64_t* seg_src, const uint64_t* seg_len,
+                                  uint32_t segments, uint64_t most_bytes, hipStream_t stream) {
+    uint64_t groups = (most_bytes + kSpliceChunk - 1) / kSpliceChunk;
+    if (groups > kSpliceMaxGroups) { groups = kSpliceMaxGroups; }
+    if (groups < 1) { groups = 1; }
+    hipLaunchKernelGGL(frame_splice_kernel, dim3((unsigned)groups), dim3(kCopyThreads), 0, stream, old, slabs, slots, dst,
+                       seg_dst, seg_src, seg_len, segments);
+}
+
+// ---------------------------------------------------------------------------------------- append
+// data_bytes more content behind a resident frame in one call ("Append"): a NEW frame of
+// content || data.  The host knows content_bytes (C), data_bytes (A) and block_bits (b), and with them t = C mod 2^b
+// (the bytes of a ragged last block), whether that block is touched (t > 0 and A > 0), keep = n_blocks - (touched ? 1 :
+// 0) blocks whose entries and streams are carried over, m = ceil((t + A) / 2^b) blocks to encode (0 for A = 0) and
+// n' = keep + m: no device count sizes a launch.  append_plan -> open for a list of at most one block -> the decode
+// chain (touched only) -> append_verdict -> the data into the staging area (range_copy_kernel, one range) -> crc32 ->
+// the encoder over the staging area -> frame_append_index -> crc32 and seal of the new index -> frame_splice.
+//
+// One lane per bitmap word and one behind them: what the open kernel takes for a list -- bit n_blocks - 1 set iff the
+// last block is touched, wpre (no bit in front of any word, wpre[words] = the count), sel[0], ctl[0] = the count -- and
+// ctl[1], the verdict on the request: EINVAL for a frame whose win_bits is not the caller's, else 0.
+__global__ __launch_bounds__(kGatherThreads)
+void append_plan_kernel(const uint8_t* __restrict__ frame, uint32_t n_blocks, uint64_t content_bytes,
+                        uint64_t data_bytes, uint32_t block_bits, uint32_t win_bits, uint32_t* __restrict__ bitmap,
+                        uint32_t* __restrict__ wpre, uint32_t* __restrict__ sel, uint32_t* __restrict__ ctl) {
+    const uint64_t words = ((uint64_t)n_blocks + 31) / 32;
+    const uint64_t w = (uint64_t)blockIdx.x * kGatherThreads + threadIdx.x;
+    const bool touched = n_blocks > 0 && data_bytes > 0 && (content_bytes & ((1ull << block_bits) - 1)) != 0;
+    if (w < words) {
+        const uint32_t last = n_blocks - 1u;
+        bitmap[w] = touched && w == (last >> 5) ? 1u << (last & 31u) : 0u;
+        wpre[w] = 0u;
+    } else if (w == words) {
+        wpre[words] = touched ? 1u : 0u;
+        if (touched) { sel[0] = n_blocks - 1u; }
+        ctl[0] = touched ? 1u : 0u;
+        ctl[1] = frame[5] != win_bits ? (uint32_t)kErrEINVAL : 0u;
+    }
+}
+
+// One workgroup, once the touched block (if any) lies decoded at the head of the staging area (entry 0 of err and crc
+// is its).  *blocks_encoded = 0 for a status of the open kernel's (the frame's own, or the other win_bits), else m.
+// *status stays what the open kernel said, else becomes the touched block's errno -- the decoder's, or EILSEQ where the
+// bytes are not the ones the index entry's CRC-32 was taken of.  The staging copy's one-range work list (copy: 5 x
+// uint64 as launch_frame_read_plan's -- src_off = copy[0] = 0, dst_off = copy + 1 = where the data starts, len_off =
+// copy + 2 = {0, data_bytes}, mask = (uint32_t*)(copy + 4)) is masked out under any status, and the encoder's blocks
+// are empty then (enc_in_off all zeros); else enc_in_off[k] = k << block_bits, the last block's end at t + data_bytes.
+// slab_off[k] = k * slab_bytes either way (m + 1 entries each).
+__global__ __launch_bounds__(256)
+void append_verdict_kernel(const uint8_t* __restrict__ frame, uint32_t n_blocks, const uint32_t* __restrict__ ctl,
+                           const int32_t* __restrict__ err, const uint32_t* __restrict__ crc, uint32_t block_bits,
+                           uint64_t content_bytes, uint64_t data_bytes, uint32_t m, uint64_t slab_bytes,
+                           int32_t* __restrict__ status, uint32_t* __restrict__ blocks_encoded,
+                           uint64_t* __restrict__ copy, uint64_t* __restrict__ enc_in_off,
+                           uint64_t* __restrict__ slab_off) {
+    __shared__ int32_t verdict;
+    const uint32_t t = threadIdx.x;
+    const uint64_t bb = 1ull << block_bits;
+    const uint64_t head = data_bytes > 0 ? content_bytes & (bb - 1) : 0;      // the touched block's bytes in front of the data
+    if (t == 0) {
+        int32_t st = *status;
+        *blocks_encoded = st != 0 ? 0u : m;
+        if (st == 0 && ctl[0] != 0) {
+            const uint32_t want = reinterpret_cast<const uint32_t*>(frame + 32)[2 * (uint64_t)(n_blocks - 1u) + 1];
+            st = err[0] != 0 ? err[0] : crc[0] != want ? kErrEILSEQ : 0;
+        }
+        *status = st;
+        verdict = st;
+        copy[0] = 0; copy[1] = head;
+        copy[2] = 0; copy[3] = data_bytes;
+        *reinterpret_cast<uint32_t*>(copy + 4) = st == 0 && data_bytes > 0 ? 1u : 0u;
+    }
+    __syncthreads();
+    const bool ok = verdict == 0;
+    const uint64_t end = head + data_bytes;
+    for (uint64_t k = t; k <= m; k += 256) {
+        enc_in_off[k] = !ok ? 0 : k * bb < end ? k * bb : end;
+        slab_off[k] = k * slab_bytes;
+    }
+}
+
+// One workgroup of 256, the scans shaped as in frame_merge_index_body: the index of the new frame from the old entries
+// of the keep blocks in front and the encoder's results for the m blocks behind them.  Each lane takes
+// ceil(n' / 256) consecutive blocks of the NEW frame.  A block below keep takes its entry from the old index; its share
+// feeds the old scan as well, whose total is the kept run's length.  A block at or above keep takes slot k = block -
+// keep: its stream in slab k (out_bytes[k], enc_err[k]), its content's CRC-32 in crc_new[k], stored by
+// frame_index_body's rule where the version stores blocks, its content then at k << block_bits of the staging area.
+// *status arrives as append_verdict_kernel left it.  Non-zero: *frame_bytes_out = 0, idx_off = {0, 0}, an empty segment
+// table, nothing else.  Else the first encoder errno in ascending order (or EINVAL for a size no entry holds), else
+// E2BIG when the new frame does not fit capacity (*frame_bytes_out = what it takes) -- again nothing of the frame is
+// written and the table is empty.  Else the header (the old magic, version, win_bits, block_bits and flags; the new
+// content_bytes, payload_bytes and n_blocks; index_crc left to frame_seal_kernel), the n' entries, the old record
+// (kDict), the padding up to payload_off = pad16(32 + 8 n' (+ 8)), idx_off = the index's range for its checksum, and
+// the table of frame_splice_kernel, m + 1 segments (seg_dst m + 2 entries, ascending; seg_src, seg_len m + 1):
+//     segment 0       the kept run, from the old frame's payload_off to the new one's (both multiples of 16); as long
+//                     as the old scan says, so the touched block's old stream is left behind
+//     segment k + 1   new block k: its slab, or its place in the staging area when it is stored (seg_len = its content's
+//                     bytes; the share is that rounded up to 8)
+template <bool kDict>
+__device__ __forceinline__
+void frame_append_index_body(const uint8_t* __restrict__ old, uint32_t n_blocks, uint64_t content_bytes,
+                             uint64_t data_bytes, uint32_t m, const uint64_t* __restrict__ out_bytes,
+                             const int32_t* __restrict__ enc_err, const uint32_t* __restrict__ crc_new,
+                             uint64_t slab_bytes, uint8_t* __restrict__ frame, uint64_t capacity,
+                             uint64_t* __restrict__ seg_dst, uint64_t* __restrict__ seg_src,
+                             uint64_t* __restrict__ seg_len, uint64_t* __restrict__ idx_off,
+                             uint64_t* __restrict__ frame_bytes_out, int32_t* __restrict__ status) {
+    __shared__ uint64_t sums_old[256];
+    __shared__ uint64_t sums_new[256];
+    __shared__ int32_t first_err[256];
+    __shared__ int32_t verdict;
+    const uint32_t t = threadIdx.x;
+    const uint64_t segments = (uint64_t)m + 1;
+    if (*status != 0) {                            // (uniform: every lane reads the same word)
+        for (uint64_t j = t; j <= segments; j += 256) {
+            seg_dst[j] = 0;
+            if (j < segments) { seg_src[j] = 0; seg_len[j] = 0; }
+        }
+        if (t == 0) { *frame_bytes_out = 0; idx_off[0] = 0; idx_off[1] = 0; }
+        return;
+    }
+    // the open kernel has passed this header: its fields are in range
+    const uint32_t* const old_index = reinterpret_cast<const uint32_t*>(old + 32);
+    const uint32_t block_bits = old[6];
+    const bool bit31 = kDict || old[4] == 2;                       // an entry's bit 31 is the stored bit
+    const bool store = kDict ? (old[7] & kFrameStored) != 0 : old[4] == 2;
+    const uint32_t words_mask = bit31 ? ~kStoredBit : 0xFFFFFFFFu;
+    const uint64_t most_words = bit31 ? 0x7FFFFFFFull : 0xFFFFFFFFull;
+    const uint64_t bb = 1ull << block_bits;
+    const uint64_t record = kDict ? 8 : 0;
+    const bool touched = n_blocks > 0 && data_bytes > 0 && (content_bytes & (bb - 1)) != 0;
+    const uint64_t keep = (uint64_t)n_blocks - (touched ? 1 : 0);
+    const uint64_t n_new = keep + m;                               // (fits 32 bits: the caller saw to it)
+    const uint64_t new_content = content_bytes + data_bytes;
+    const uint64_t old_payload_off = (32 + 8 * (uint64_t)n_blocks + record + 15) & ~(uint64_t)15;
+    const uint64_t payload_off = (32 + 8 * n_new + record + 15) & ~(uint64_t)15;
+    const uint64_t per = (n_new + 255) / 256;
+    const uint64_t b0 = t * per < n_new ? t * per : n_new;
+    const uint64_t b1 = b0 + per < n_new ? b0 + per : n_new;
+    uint64_t sum_old = 0, sum_new = 0;
+    int32_t bad = 0;
+    for (uint64_t b = b0; b < b1; b++) {
+        if (b < keep) {
+            const uint64_t share = (uint64_t)(old_index[2 * b] & words_mask) * 8;
+            sum_old += share;
+            sum_new += share;
+        } else {
+            const uint64_t k = b - keep;
+            const uint64_t v = out_bytes[k];
+            if (bad == 0 && enc_err[k] != 0) { bad = enc_err[k]; }
+            if (bad == 0 && ((v & 7u) != 0 || (v >> 3) > most_words)) { bad = kErrEINVAL; }
+            sum_new += store ? payload_share(v, block_len(b, bb, new_content)) : v;
+        }
+    }
+    sums_old[t] = sum_old;
+    sums_new[t] = sum_new;
+    first_err[t] = bad;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t run_old = 0, run_new = 0;
+        int32_t st = 0;
+        for (int k = 0; k < 256; k++) {
+            const uint64_t vn = sums_new[k];
+            run_old += sums_old[k];
+            sums_new[k] = run_new;
+            run_new += vn;
+            if (st == 0) { st = first_err[k]; }
+        }
+        const uint64_t frame_bytes = payload_off + run_new;
+        if (st == 0 && frame_bytes > capacity) { st = kErrE2BIG; }
+        verdict = st;
+        *status = st;
+        *frame_bytes_out = st == 0 || st == kErrE2BIG ? frame_bytes : 0;
+        idx_off[0] = st == 0 ? 32 : 0;
+        idx_off[1] = st == 0 ? 32 + 8 * n_new + record : 0;
+        if (st == 0) {
+            const uint32_t* const oh = reinterpret_cast<const uint32_t*>(old);
+            uint32_t* const h = reinterpret_cast<uint32_t*>(frame);
+            h[0] = oh[0]; h[1] = oh[1];                            // magic; version, win_bits, block_bits, flags
+            h[2] = (uint32_t)new_content; h[3] = (uint32_t)(new_content >> 32);
+            h[4] = (uint32_t)run_new; h[5] = (uint32_t)(run_new >> 32);
+            h[6] = (uint32_t)n_new;
+            h[7] = 0u;                                             // index_crc: frame_seal_kernel
+            const uint32_t* const old_behind = oh + 8 + 2 * (uint64_t)n_blocks;
+            uint32_t* const behind = h + 8 + 2 * n_new;
+            if (kDict) {
+                behind[0] = old_behind[0]; behind[1] = old_behind[1];
+                if ((n_new & 1u) == 0) { behind[2] = 0u; behind[3] = 0u; }
+            } else if ((n_new & 1u) != 0) { behind[0] = 0u; behind[1] = 0u; }
+            seg_dst[0] = payload_off; seg_src[0] = kSegOld | old_payload_off; seg_len[0] = run_old;
+            seg_dst[segments] = frame_bytes;                       // (m = 0: the kept run's end)
+        }
+    }
+    __syncthreads();
+    if (verdict != 0) {
+        for (uint64_t j = t; j <= segments; j += 256) {
+            seg_dst[j] = 0;
+            if (j < segments) { seg_src[j] = 0; seg_len[j] = 0; }
+        }
+        return;
+    }
+    uint32_t* const index = reinterpret_cast<uint32_t*>(frame + 32);
+    uint64_t at = payload_off + sums_new[t];
+    for (uint64_t b = b0; b < b1; b++) {
+        uint64_t share;
+        if (b < keep) {
+            const uint32_t e = old_index[2 * b];
+            share = (uint64_t)(e & words_mask) * 8;
+            index[2 * b] = e;
+            index[2 * b + 1] = old_index[2 * b + 1];
+        } else {
+            const uint64_t k = b - keep;
+            const uint64_t v = out_bytes[k];
+            const uint64_t len = block_len(b, bb, new_content);
+            const bool st = store && block_stored(v, len);
+            share = store ? payload_share(v, len) : v;
+            index[2 * b] = (uint32_t)(share >> 3) | (st ? kStoredBit : 0u);
+            index[2 * b + 1] = crc_new[k];
+            seg_dst[k + 1] = at;
+            seg_src[k + 1] = st ? kSegSlot | (k * bb) : kSegSlab | (k * slab_bytes);
+            seg_len[k + 1] = st ? len : share;
+        }
+        at += share;
+    }
+}
+
+__global__ __launch_bounds__(256)
+void frame_append_index_kernel(const uint8_t* __restrict__ old, uint32_t n_blocks, uint64_t content_bytes,
+                               uint64_t data_bytes, uint32_t m, const uint64_t* __restrict__ out_bytes,
+                               const int32_t* __restrict__ enc_err, const uint32_t* __restrict__ crc_new,
+                               uint64_t slab_bytes, uint8_t* __restrict__ frame, uint64_t capacity,
+                               uint64_t* __restrict__ seg_dst, uint64_t* __restrict__ seg_src,
+                               uint64_t* __restrict__ seg_len, uint64_t* __restrict__ idx_off,
+                               uint64_t* __restrict__ frame_bytes_out, int32_t* __restrict__ status) {
+    frame_append_index_body<false>(old, n_blocks, content_bytes, data_bytes, m, out_bytes, enc_err, crc_new, slab_bytes,
+                                   frame, capacity, seg_dst, seg_src, seg_len, idx_off, frame_bytes_out, status);
+}
+
+__global__ __launch_bounds__(256)
+void frame_append_index_v3_kernel(const uint8_t* __restrict__ old, uint32_t n_blocks, uint64_t content_bytes,
+                                  uint64_t data_bytes, uint32_t m, const uint64_t* __restrict__ out_bytes,
+                                  const int32_t* __restrict__ enc_err, const uint32_t* __restrict__ crc_new,
+                                  uint64_t slab_bytes, uint8_t* __restrict__ frame, uint64_t capacity,
+                                  uint64_t* __restrict__ seg_dst, uint64_t* __restrict__ seg_src,
+                                  uint64_t* __restrict__ seg_len, uint64_t* __restrict__ idx_off,
+                                  uint64_t* __restrict__ frame_bytes_out, int32_t* __restrict__ status) {
+    frame_append_index_body<true>(old, n_blocks, content_bytes, data_bytes, m, out_bytes, enc_err, crc_new, slab_bytes,
+                                  frame, capacity, seg_dst, seg_src, seg_len, idx_off, frame_bytes_out, status);
+}
+
+void launch_append_plan(const uint8_t* frame, uint32_t n_blocks, uint64_t content_bytes, uint64_t data_bytes,
+                        uint32_t block_bits, uint32_t win_bits, uint32_t* bitmap, uint32_t* wpre, uint32_t* sel,
+                        uint32_t* ctl, hipStream_t stream) {
+    const uint64_t words = ((uint64_t)n_blocks + 31) / 32;
+    const uint64_t grid = (words + 1 + kGatherThreads - 1) / kGatherThreads;
+    hipLaunchKernelGGL(append_plan_kernel, dim3((unsigned)grid), dim3(kGatherThreads), 0, stream, frame, n_blocks,
+                       content_bytes, data_bytes, block_bits, win_bits, bitmap, wpre, sel, ctl);
+}
+
+void launch_append_verdict(const uint8_t* frame, uint32_t n_blocks, const uint32_t* ctl, const int32_t* err,
+                           const uint32_t* crc, uint32_t block_bits, uint64_t content_bytes, uint64_t data_bytes,
+                           uint32_t m, uint64_t slab_bytes, int32_t* status, uint32_t* blocks_encoded, uint64_t* copy,
+                           uint64_t* enc_in_off, uint64_t* slab_off, hipStream_t stream) {
+    hipLaunchKernelGGL(append_verdict_kernel, dim3(1), dim3(256), 0, stream, frame, n_blocks, ctl, err, crc, block_bits,
+                       content_bytes, data_bytes, m, slab_bytes, status, blocks_encoded, copy, enc_in_off, slab_off);
+}
+
+void launch_frame_append_index(const uint8_t* old, uint32_t n_blocks, uint64_t content_bytes, uint64_t data_bytes,
+                               uint32_t m, bool dict, const uint64_t* out_bytes, const int32_t* enc_err,
+                               const uint32_t* crc_new, uint64_t slab_bytes, uint8_t* frame, uint64_t capacity,
+                               uint64_t* seg_dst, uint64_t* seg_src, uint64_t* seg_len, uint64_t* idx_off,
+                               uint64_t* frame_bytes_out, int32_t* status, hipStream_t stream) {
+    if (dict) {
+        hipLaunchKernelGGL(frame_append_index_v3_kernel, dim3(1), dim3(256), 0, stream, old, n_blocks, content_bytes,
+                           data_bytes, m, out_bytes, enc_err, crc_new, slab_bytes, frame, capacity, seg_dst, seg_src,
+                           seg_len, idx_off, frame_bytes_out, status);
+    } else {
+        hipLaunchKernelGGL(frame_append_index_kernel, dim3(1), dim3(256), 0, stream, old, n_blocks, content_bytes,
+                           data_bytes, m, out_bytes, enc_err, crc_new, slab_bytes, frame, capacity, seg_dst, seg_src,
+                           seg_len, idx_off, frame_bytes_out, status);
+    }
+}
+
 } // namespace sqzk

@@ -211,5 +211,36 @@ void launch_frame_merge_index(const uint8_t* old, uint32_t n_blocks, uint64_t co
 void launch_frame_splice(const uint8_t* old, const uint8_t* slabs, const uint8_t* slots, uint8_t* dst,
                          const uint64_t* seg_dst, const uint64_t* seg_src, const uint64_t* seg_len, uint32_t max_blocks,
                          uint64_t most_bytes, hipStream_t stream);
+// splice over a table of `segments` segments (seg_dst: segments + 1 entries)
+void launch_frame_splice_segments(const uint8_t* old, const uint8_t* slabs, const uint8_t* slots, uint8_t* dst,
+                                  const uint64_t* seg_dst, const uint64_t* seg_src, const uint64_t* seg_len,
+                                  uint32_t segments, uint64_t most_bytes, hipStream_t stream);
+
+// data_bytes more content behind a resident frame in one call (frame.hip, "append").  The host
+// knows t = content_bytes mod 2^block_bits, whether the last block is touched (t > 0 and data_bytes > 0), keep =
+// n_blocks - (touched ? 1 : 0) and m = ceil((t + data_bytes) / 2^block_bits) (0 for no data).
+// plan: bitmap (ceil(n_blocks / 32) words), wpre (words + 1), sel (1 entry) and ctl[0] for launch_frame_open_list with
+//   max_blocks = 1 -- the last block iff it is touched -- and ctl[1] = EINVAL for a frame whose win_bits is another
+//   (ctl: 2 words).
+// verdict: after the decode chain (entry 0 of err / crc is the touched block's); *blocks_encoded = 0 under a status of
+//   the open's, else m; *status = the open's, else the touched block's errno or EILSEQ; copy (5 x uint64): the one-range
+//   work list launch_range_copy(data, copy, staging, copy + 1, copy + 2, (uint32_t*)(copy + 4), 1, ..) of the data to
+//   staging + t, masked out under any status; enc_in_off / slab_off (m + 1 entries): the encoder's blocks over the
+//   staging area (all empty under any status) and their slabs.
+// append_index: the new frame's header, n' = keep + m entries, record and padding from the old entries and the
+//   encoder's results (out_bytes, enc_err, crc_new: m entries), *frame_bytes_out, *status (the encoder's errno, E2BIG),
+//   idx_off for the index checksum, and the segment table: seg_dst m + 2 entries, seg_src / seg_len m + 1.
+void launch_append_plan(const uint8_t* frame, uint32_t n_blocks, uint64_t content_bytes, uint64_t data_bytes,
+                        uint32_t block_bits, uint32_t win_bits, uint32_t* bitmap, uint32_t* wpre, uint32_t* sel,
+                        uint32_t* ctl, hipStream_t stream);
+void launch_append_verdict(const uint8_t* frame, uint32_t n_blocks, const uint32_t* ctl, const int32_t* err,
+                           const uint32_t* crc, uint32_t block_bits, uint64_t content_bytes, uint64_t data_bytes,
+                           uint32_t m, uint64_t slab_bytes, int32_t* status, uint32_t* blocks_encoded, uint64_t* copy,
+                           uint64_t* enc_in_off, uint64_t* slab_off, hipStream_t stream);
+void launch_frame_append_index(const uint8_t* old, uint32_t n_blocks, uint64_t content_bytes, uint64_t data_bytes,
+                               uint32_t m, bool dict, const uint64_t* out_bytes, const int32_t* enc_err,
+                               const uint32_t* crc_new, uint64_t slab_bytes, uint8_t* frame, uint64_t capacity,
+                               uint64_t* seg_dst, uint64_t* seg_src, uint64_t* seg_len, uint64_t* idx_off,
+                               uint64_t* frame_bytes_out, int32_t* status, hipStream_t stream);
 
 } // namespace sqzk

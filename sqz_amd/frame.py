@@ -5,6 +5,7 @@ Every byte of codec and checksum work happens in libsqz_amd.so; nothing is compu
 
     python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18] [--store] [--lazy] [--dict FILE]   compress a file
     python -m sqz_amd.frame d IN OUT [--dict FILE]                         decompress one
+    python -m sqz_amd.frame a FRAME IN OUT [--lazy] [--dict FILE]          append IN's bytes to FRAME (append_frame)
     python -m sqz_amd.frame info IN                                        describe one
     python -m sqz_amd.frame blocks IN                                      one line per block
 
@@ -474,6 +475,77 @@ def update_frame(d_frame, offsets, lengths, data, max_length: int = None, max_bl
     return d_out, frame_bytes, data_off, range_err[:count], blocks_encoded, status
 
 
+def _frame_bound_of(info: dict, content: int, bits: int) -> int:
+    """a capacity that is always enough for a frame of `content` bytes at the version of `info`"""
+    L = N.lib()
+    if info["version"] == 3:                                 # with or without stored blocks: the larger bound
+        return int(max(L.sqz_frame_bound_dict(content, bits, FRAME_DICT),
+                       L.sqz_frame_bound_dict(content, bits, FRAME_DICT | FRAME_STORED)))
+    if info["version"] == 2:
+        return int(L.sqz_frame_bound_ex(content, bits, FRAME_STORED))
+    return int(L.sqz_frame_bound(content, bits))
+
+
+def append_frame(d_frame, data, d_out=None, info: dict = None, dictionary=None, parse="greedy", scratch=None):
+    """More content behind a device-resident frame in one call: the new frame, in d_out (uint8, of the version's bound
+    of the longer content when not given; it must not overlap d_frame), is the frame of content || data -- byte for
+    byte the encoder's frame of it with the same parse.  Only a ragged last block is decoded, verified and encoded again
+    with the data behind it; every other stream is carried over as it lies.  data: bytes-like or a one-dimensional
+    uint8 device tensor (anything else is ValueError).  `info` and dictionary as for gather_frame.  The scratch takes
+    about 11 bytes per byte of data: a long append goes in pieces, and two appends leave the frame of one.
+    Enqueues and returns (d_out, frame_bytes int64[1], blocks_encoded int32[1], status int32[1]), all device tensors:
+    d_out[:frame_bytes] is the new frame when status is 0 after a synchronise, and d_out is untouched otherwise.
+    status: the frame's own; the last block's decode or checksum error; an encoder's errno; E2BIG when d_out is too
+    small (frame_bytes says what it takes)."""
+    import torch
+    L = N.lib()
+    parse = parse_code(parse)
+    if info is None:
+        info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    n, content, bits = info["n_blocks"], info["content_bytes"], info["block_bytes"].bit_length() - 1
+    device = d_frame.device
+    d = _dict_dev(dictionary, 1 << info["win_bits"], device) if dictionary is not None else None
+    if isinstance(data, torch.Tensor):
+        if data.dtype != torch.uint8 or data.dim() != 1:
+            raise ValueError("append_frame: data tensor must be one-dimensional uint8")
+        d_data = data.contiguous().to(device)
+    else:
+        try:
+            host = bytes(memoryview(data))
+        except TypeError:
+            raise ValueError("append_frame: data must be bytes-like or a one-dimensional uint8 tensor") from None
+        d_data = torch.frombuffer(bytearray(host or b"\0"), dtype=torch.uint8)[:len(host)].to(device)
+    count = d_data.numel()
+    if d_out is None:
+        d_out = torch.empty(max(_frame_bound_of(info, content + count, bits), 16), dtype=torch.uint8, device=device)
+    frame_bytes = torch.zeros(1, dtype=torch.int64, device=device)
+    blocks_encoded = torch.zeros(1, dtype=torch.int32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    if scratch is None:
+        scratch = _scratch_for(device, int(L.sqz_hip_frame_append_scratch_bytes(n, content, count, bits,
+                                                                                  d.numel() if d is not None else 0)))
+    head = (_ptr(d_frame), d_frame.numel(), n, content, info["win_bits"], bits, _ptr(d_data) if count else None, count,
+            parse)
+    tail = (_ptr(d_out), d_out.numel(), _ptr(frame_bytes), _ptr(blocks_encoded), _ptr(status), _ptr(scratch),
+            scratch.numel(), _stream())
+    if d is not None:
+        _raise(L.sqz_hip_frame_append_dict(*head, _ptr(d), d.numel(), *tail), "sqz_hip_frame_append_dict")
+    else:
+        _raise(L.sqz_hip_frame_append(*head, *tail), "sqz_hip_frame_append")
+    return d_out, frame_bytes, blocks_encoded, status
+
+
+def _append_file(frame: bytes, data: bytes, dictionary, parse: str) -> bytes:
+    """the file tool's `a`: FRAME and IN through append_frame, the new frame as bytes (SqzError on a status)"""
+    import torch
+    d_frame = torch.frombuffer(bytearray(frame) + bytearray(16), dtype=torch.uint8)[:len(frame)].to("cuda")
+    d_out, frame_bytes, _, status = append_frame(d_frame, data, info=frame_info(frame), dictionary=dictionary,
+                                                 parse=parse)
+    torch.cuda.synchronize()
+    _raise(int(status.item()), "append_frame (status)")
+    return d_out[:int(frame_bytes.item())].cpu().numpy().tobytes()
+
+
 # ---- file tool ----------------------------------------------------------------------------------
 def main(argv=None) -> int:
     import argparse
@@ -492,6 +564,12 @@ def main(argv=None) -> int:
     d.add_argument("src")
     d.add_argument("dst")
     d.add_argument("--dict", dest="dictionary", metavar="FILE", help="the dictionary a version-3 frame was written with")
+    p = sub.add_parser("a", help="append IN's bytes to FRAME, write OUT")
+    p.add_argument("frame")
+    p.add_argument("src")
+    p.add_argument("dst")
+    p.add_argument("--lazy", action="store_true", help="lazy parse for the blocks that are encoded")
+    p.add_argument("--dict", dest="dictionary", metavar="FILE", help="the dictionary a version-3 frame was written with")
     i = sub.add_parser("info", help="describe IN")
     i.add_argument("src")
     k = sub.add_parser("blocks", help="one line per block of IN")
@@ -510,6 +588,9 @@ def main(argv=None) -> int:
                 out = compress_frame(blob, a.win_bits, a.block_bits, a.store, parse)
             else:
                 out = compress_frame(blob, a.win_bits, a.block_bits, a.store, parse, dictionary=dct)
+        elif a.cmd == "a":
+            with open(a.frame, "rb") as fh:
+                out = _append_file(fh.read(), blob, dct, "lazy" if a.lazy else "greedy")
         elif a.cmd == "d":
             out = decompress_frame(blob) if dct is None else decompress_frame(blob, dictionary=dct)
         elif a.cmd == "blocks":
