@@ -378,7 +378,7 @@ void huffman_emit_kernel(const uint32_t* __restrict__ tokens,
 #ifdef SQZ_EMU_DEBUG_BATCH
         if (lane == 0) {
             static unsigned dbg_steps = 0, dbg_offered = 0, dbg_applied = 0, dbg_exact = 0, dbg_next = 16384;
-            dbg_steps++; dbg_offered += (unsigned)offered; dbg_applied += (unsigned)m; dbg_exact += (m < offered || offered == 0 || frozen) ? 1u : 0u;
+            dbg_steps++; dbg_offered += (unsigned)offered - g_dbg_cut; g_dbg_cut = 0; dbg_applied += (unsigned)m; dbg_exact += (m < offered || offered == 0 || frozen) ? 1u : 0u;
             if (cursor >= dbg_next || cursor >= count) {
                 fprintf(stderr, "cursor %u: steps %u offered %u applied %u exact %u (want %d) depth %d/%d aux %d/%d\n", cursor, dbg_steps, dbg_offered, dbg_applied, dbg_exact, want,
                         lit.depth, pos.depth, lit.aux, pos.aux);

@@ -34,11 +34,25 @@
 // remembers those two leaves (not the numbers: an insert shifts positions, leaf identities stay).
 // With P = inclusive prefix sums of the batch's histogram over positions,
 // n(v) = P[pos(last(v))] - P[pos(first(v)) - 1] for ALL nodes at once: independent lookups per
-// node (eight probes per lane) instead of two dependent walks per token with an LDS atomic on every
+// node (seven probes per lane) instead of two dependent walks per token with an LDS atomic on every
 // level.  A node's test partner (sibling for a lo child, uncle for a hi child) is cached next to
 // its ends.  If node v fails its test, the first token that may not be applied is the
 // (f(partner) - f(v) + 1)-th one whose position lies below v; the earliest such token over all
-// failing nodes ends the batch.  tests/model/range_model.c is the first form of this algorithm
+// failing nodes ends the batch.
+//
+// TWO THINGS A STEP DOES NOT PAY FOR.  (1) The internal nodes are probed one per lane and row.  The
+// literal tree's 288 fill four rows of 64 and half of a fifth; the distance tree's (32 at most) take
+// the other half of that row instead of a row of their own: both trees live in the same arrays under
+// absolute ids and their leaf positions do not overlap, so probe, test, locate and update are the
+// same code for a node of either tree.  (2) A token whose own leaf has no slack (it has a partner
+// and the partner's count does not exceed the leaf's) is the first token that may not pass that
+// leaf, and where a node stops the batch does not depend on what is offered behind that token: the
+// offer is cut there from the two counts that level 2 has read anyway, BEFORE anything is counted.
+// The batch then applies exactly what it would have applied (the step lengths, and with them the
+// callers' offer policies, are unchanged), but four in ten of the batches that used to fail now pass
+// on the first count, and the others locate fewer failing nodes in a shorter offer.
+//
+// tests/model/range_model.c is the first form of this algorithm
 // (numeric intervals) in plain C, held against the oracle's tree in lockstep
 // (tests/test_range_model.py); the kernels themselves run on the CPU in tests/emu.
 //
@@ -108,6 +122,10 @@ constexpr int kStack = 128;                   // deepest chain the one-lane path
 constexpr int kTokenBits = 2 * (kAuxDepth - 1) + 18;
 constexpr int kPackWords = (63 + 58 + kWave * kTokenBits + 63) / 64 + 1;     // carry + pending + 64 tokens
 constexpr int kImageWords = kPackWords > kWave ? kPackWords : kWave;         // (the histogram takes 64 words)
+
+#ifdef SQZ_EMU_DEBUG_BATCH
+static unsigned g_dbg_cut;                    // emulator builds only: tokens taken off the offers before they were counted
+#endif
 
 #if defined(SQZ_STATS) && defined(SQZ_SEC_TIMERS)
 __device__ unsigned long long g_sec[32];
@@ -1298,29 +1316,38 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
     // (zero, add, read, scan, write) runs while the level-2 reads are on their way.
     SEC_BEGIN
     const bool take = lane < m;
-    const bool has_a = take && a >= 0, has_b = take && b >= 0;
+    bool has_a = take && a >= 0, has_b = take && b >= 0;
     const int ia = has_a ? a : LIT::kRoot - 1, ib = has_b ? b : POS::kRoot - 1;      // (idle lanes look at a pad leaf)
-    constexpr int kLitRows = (kLitNodes - kLitLeaves + kWave - 1) / kWave;      // 5
-    constexpr int kRows = kLitRows + 1;                                         // + the distance tree's row
+    // The internal nodes of BOTH trees, one per lane and row.  The literal tree's fill four rows and half
+    // of a fifth; the distance tree's (32 at most) take the other half of that row: the trees share the
+    // LDS arrays under absolute ids and their leaf positions do not overlap, so a probe, its test and its
+    // update are the same code for a node of either tree.
+    constexpr int kLitInner = kLitNodes - kLitLeaves, kPosInner = kPosNodes - kPosLeaves;
+    constexpr int kLitRows = (kLitInner + kWave - 1) / kWave;                   // 5
+    constexpr int kLastRow = kLitRows - 1, kLastLit = kLastRow * kWave;         // the shared row; its first literal node
+    static_assert(kLitInner % kWave != 0 && kLitInner % kWave <= kWave / 2, "the literal tree leaves half of its last row free");
+    static_assert(kPosInner <= kWave / 2, "the distance tree's internal nodes fit that half row");
+    static_assert(kPosPos0 >= kLitLeaves, "the leaf positions of the two trees do not overlap");
     // ---- level 1: range word and count of the tokens' leaves and of this lane's internal nodes ----------
-    int vi[kRows];
-    bool on[kRows];
+    int vi[kLitRows];
+    bool on[kLitRows];
 #pragma unroll
-    for (int row = 0; row < kLitRows; row++) {
+    for (int row = 0; row < kLastRow; row++) {
         const int v = LIT::kRoot + row * kWave + lane;
         on[row] = v < lit.next && v != LIT::kRoot;
         vi[row] = on[row] ? v : LIT::kRoot;
     }
     {
-        const int v = POS::kRoot + lane;
-        on[kLitRows] = v < pos.next && v != POS::kRoot;
-        vi[kLitRows] = on[kLitRows] ? v : POS::kRoot;
+        const bool in_pos = lane >= kWave / 2;
+        const int v = in_pos ? POS::kRoot + lane - kWave / 2 : LIT::kRoot + kLastLit + lane;
+        on[kLastRow] = in_pos ? (v < pos.next && v != POS::kRoot) : v < lit.next;
+        vi[kLastRow] = on[kLastRow] ? v : (in_pos ? POS::kRoot : LIT::kRoot);
     }
     const uint32_t ra = lds->rng[ia], rb = lds->rng[ib];
     const uint32_t wa = lds->cnt[ia], wb = lds->cnt[ib];
-    uint32_t rw[kRows], cw[kRows];
+    uint32_t rw[kLitRows], cw[kLitRows];
 #pragma unroll
-    for (int k = 0; k < kRows; k++) { rw[k] = lds->rng[vi[k]]; cw[k] = lds->cnt[vi[k]]; }
+    for (int k = 0; k < kLitRows; k++) { rw[k] = lds->rng[vi[k]]; cw[k] = lds->cnt[vi[k]]; }
     if (kWantCode) {
         code_a = code[has_a ? ia - LIT::kBase + 0 : 0];
         code_b = code[has_b ? ib - POS::kBase + kPosPos0 : 0];
@@ -1331,9 +1358,9 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
     // ---- level 2: partners' counts, the ends' positions (on their way while the histogram is made) -------
     const uint32_t pa_a = r_pa(ra), pa_b = r_pa(rb);
     const uint32_t cpa = lds->cnt[pa_a != kNil ? pa_a : (uint32_t)ia], cpb = lds->cnt[pa_b != kNil ? pa_b : (uint32_t)ib];
-    uint32_t cp[kRows], rf[kRows], rl[kRows];
+    uint32_t cp[kLitRows], rf[kLitRows], rl[kLitRows];
 #pragma unroll
-    for (int k = 0; k < kRows; k++) {
+    for (int k = 0; k < kLitRows; k++) {
         const uint32_t pk = r_pa(rw[k]);
         cp[k] = lds->cnt[pk != kNil ? pk : (uint32_t)vi[k]];
         rf[k] = lds->rng[r_first(rw[k])];
@@ -1341,9 +1368,11 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
     }
     SEC(0)
     // ---- histogram over positions (a byte each), then its prefix sums in place ----------------
-    auto histogram = [&](int upto) {
+    auto clear_histogram = [&]() {
         lds->P64[lane] = 0ull;
         lds_fence();
+    };
+    auto histogram = [&](int upto) {
         if (lane < upto && has_a) { atomicAdd(&lds->P32[qa >> 2], 1u << (8u * (qa & 3u))); }
         if (lane < upto && has_b) { atomicAdd(&lds->P32[qb >> 2], 1u << (8u * (qb & 3u))); }
         lds_fence();
@@ -1356,15 +1385,52 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
         lds->P64[lane] = (incl << 8) + (uint64_t)base * 0x0101010101010101ull;     // exclusive: P[i] = symbols at positions < i
         lds_fence();
     };
+    clear_histogram();                                   // (does not depend on the cut below: issued before its wait)
+    // ---- a token whose own leaf has no slack (its partner's count does not exceed the leaf's) ends the
+    //      batch whatever else is offered: it is the first token that may not pass that leaf, and where a
+    //      node stops the batch does not depend on what is offered behind that token.  Both counts are in
+    //      registers already, so the offer ends there before anything is counted: the batch then passes its
+    //      tests on the first count, or has fewer failing nodes to locate. -----------------------------------
+#ifdef SQZ_EMU_DEBUG_BATCH                        // one line per call: the offer, who would cut it, which tests failed
+    const int dbg_m = m;
+    const uint64_t dbg_sa = __ballot(has_a && pa_a != kNil && c_f(cpa) <= c_f(wa));
+    const uint64_t dbg_sb = __ballot(has_b && pa_b != kNil && c_f(cpb) <= c_f(wb));
+    const uint64_t dbg_nil = __ballot((has_a && pa_a == kNil) || (has_b && pa_b == kNil));
+    uint64_t dbg_bad[2 + kLitRows] = {};
+    auto dbg_line = [&](int cut, int applied) {
+        if (lane != 0) { return; }
+        fprintf(stderr, "batch m %d cut %d a %llx b %llx nil %llx bad", dbg_m, cut, (unsigned long long)dbg_sa,
+                (unsigned long long)dbg_sb, (unsigned long long)dbg_nil);
+        for (int c = 0; c < 2 + kLitRows; c++) { fprintf(stderr, " %llx", (unsigned long long)dbg_bad[c]); }
+        fprintf(stderr, " ok %d next %d %d\n", applied, lit.next - LIT::kRoot, pos.next - POS::kRoot);
+    };
+#endif
+#ifndef SQZ_BATCH_NO_CUT                          // (measurements and tests: the offer as the caller made it)
+    {
+        const uint64_t stops = __ballot((has_a && pa_a != kNil && c_f(cpa) <= c_f(wa)) ||
+                                        (has_b && pa_b != kNil && c_f(cpb) <= c_f(wb)));
+        if (stops != 0) {
+            const int j = __builtin_ctzll(stops);
+#ifdef SQZ_EMU_DEBUG_BATCH
+            if (lane == 0) { g_dbg_cut += (unsigned)(m - j); }
+            if (j == 0) { dbg_line(0, 0); }
+#endif
+            m = j;                                         // (j < m: only offered lanes vote)
+            if (m == 0) { return 0; }                      // nothing may be applied: the first token takes the exact path
+            has_a = has_a && lane < m;
+            has_b = has_b && lane < m;
+        }
+    }
+#endif
     histogram(m);
     SEC(1)
     // ---- level 3: how many of the batch's chains pass each node (its position run in the prefix sums) ---
-    uint32_t st[kRows], en[kRows], pst[kRows], pen[kRows];
+    uint32_t st[kLitRows], en[kLitRows], pst[kLitRows], pen[kLitRows];
 #pragma unroll
-    for (int k = 0; k < kRows; k++) { st[k] = r_pos(rf[k]); en[k] = r_pos(rl[k]) + 1u; }
+    for (int k = 0; k < kLitRows; k++) { st[k] = r_pos(rf[k]); en[k] = r_pos(rl[k]) + 1u; }
     const uint32_t p_a0 = lds->P8[qa], p_a1 = lds->P8[qa + 1u], p_b0 = lds->P8[qb], p_b1 = lds->P8[qb + 1u];
 #pragma unroll
-    for (int k = 0; k < kRows; k++) { pst[k] = lds->P8[st[k]]; pen[k] = lds->P8[en[k]]; }
+    for (int k = 0; k < kLitRows; k++) { pst[k] = lds->P8[st[k]]; pen[k] = lds->P8[en[k]]; }
     // ---- every touched node's test: f + n <= count of its partner (a lo child's sibling, a hi child's
     //      uncle); the tokens' own leaves first (duplicates test the same node twice: harmless) -------------
     // per tested node, kept in a register: its position run and how many chains may still pass it
@@ -1373,8 +1439,8 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
         const uint32_t allowed = fb > f ? fb - f : 0u;
         return s0 | (e0 << 9) | ((allowed < 255u ? allowed : 255u) << 18);
     };
-    uint32_t nl[kLitRows], sel[kLitRows], np = 0, sep = 0;     // per row: chains through my node, its packed test
-    uint32_t bad = 0;                                   // bit 0 / 1: my leaves; bit 2 + r: my node of lit row r; bit 7: pos row
+    uint32_t nl[kLitRows], sel[kLitRows];               // per row: chains through my node, its packed test
+    uint32_t bad = 0;                                   // bit 0 / 1: my leaves; bit 2 + r: my node of row r
     uint32_t sa, sb;
     {
         const uint32_t n = has_a ? p_a1 - p_a0 : 0u, f = c_f(wa), fb = c_f(cpa);
@@ -1387,24 +1453,26 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
         bad |= (n != 0 && pa_b != kNil && f + n > fb) ? 2u : 0u;
     }
 #pragma unroll
-    for (int k = 0; k < kRows; k++) {
+    for (int k = 0; k < kLitRows; k++) {
         const uint32_t n = on[k] ? pen[k] - pst[k] : 0u, f = c_f(cw[k]), fb = c_f(cp[k]);
-        const uint32_t packed = on[k] ? pack(st[k], en[k], f, fb) : 0u;
-        const bool fails = n != 0 && r_pa(rw[k]) != kNil && f + n > fb;
-        if (k < kLitRows) { nl[k] = n; sel[k] = packed; bad |= fails ? (4u << k) : 0u; }
-        else { np = n; sep = packed; bad |= fails ? 128u : 0u; }
+        nl[k] = n;
+        sel[k] = on[k] ? pack(st[k], en[k], f, fb) : 0u;
+        bad |= (n != 0 && r_pa(rw[k]) != kNil && f + n > fb) ? (4u << k) : 0u;
     }
     int ok = m;
     SEC(2)
+#ifdef SQZ_EMU_DEBUG_BATCH
+    for (int c = 0; c < 2 + kLitRows; c++) { dbg_bad[c] = __ballot((bad >> c) & 1u); }
+#endif
     if (__ballot(bad != 0) != 0) {
         // some node would overtake its partner.  For each such node, the token that may not pass is
         // the (partner's count - its count + 1)-th one whose position lies below the node; the
         // earliest of them over all failing nodes ends the batch.  The failing lane's registers
         // hold all that is needed.
 #pragma unroll
-        for (int cat = 0; cat < 8; cat++) {
+        for (int cat = 0; cat < 2 + kLitRows; cat++) {
             uint64_t vm = __ballot((bad >> cat) & 1u);
-            const uint32_t mine = cat == 0 ? sa : cat == 1 ? sb : cat == 7 ? sep : sel[cat >= 2 && cat < 7 ? cat - 2 : 0];
+            const uint32_t mine = cat == 0 ? sa : cat == 1 ? sb : sel[cat >= 2 ? cat - 2 : 0];
             while (vm != 0) {
                 const int k = __builtin_ctzll(vm);
                 vm &= vm - 1;
@@ -1416,14 +1484,17 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
                 if (first_bad != 0) { const int j = __builtin_ctzll(first_bad); ok = j < ok ? j : ok; }
             }
         }
+#ifdef SQZ_EMU_DEBUG_BATCH
+        if (ok == 0) { dbg_line(m < dbg_m ? m : -1, 0); }
+#endif
         if (ok == 0) { return 0; }                              // nothing may be applied: the first token takes the exact path
         // count again for the prefix only (the nodes' position runs are still in registers)
+        clear_histogram();
         histogram(ok);
 #pragma unroll
         for (int row = 0; row < kLitRows; row++) {
             nl[row] = (uint32_t)lds->P8[(sel[row] >> 9) & 0x1FFu] - (uint32_t)lds->P8[sel[row] & 0x1FFu];
         }
-        np = (uint32_t)lds->P8[(sep >> 9) & 0x1FFu] - (uint32_t)lds->P8[sep & 0x1FFu];
     }
     SEC(3)
     // ---- apply the prefix: leaves one add per token (lanes holding the same symbol meet at its
@@ -1432,12 +1503,13 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
     if (lane < ok && has_b) { atomicAdd(&lds->cnt[ib], 1u); }
 #pragma unroll
     for (int row = 0; row < kLitRows; row++) {
-        const int v = LIT::kRoot + row * kWave + lane;
-        if (nl[row] != 0) { atomicAdd(&lds->cnt[v], nl[row]); }       // (one LDS instruction instead of read + write)
+        if (nl[row] != 0) { atomicAdd(&lds->cnt[vi[row]], nl[row]); }   // (one LDS instruction instead of read + write)
     }
-    if (np != 0) { atomicAdd(&lds->cnt[POS::kRoot + lane], np); }
     lds_fence();
     SEC(4)
+#ifdef SQZ_EMU_DEBUG_BATCH
+    dbg_line(m < dbg_m ? m : -1, ok);
+#endif
     return ok;
 }
 
