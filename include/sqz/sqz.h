@@ -370,7 +370,8 @@ enum {
     sqz_frame_max_block_bits = 24
 };
 enum { SQZ_FRAME_STORED = 1,     /* flags: store a block raw when its stream is not smaller (version 2) */
-       SQZ_FRAME_DICT = 2 };     /* flags: every block may reach back into one shared dictionary (version 3, below) */
+       SQZ_FRAME_DICT = 2,       /* flags: every block may reach back into one shared dictionary (version 3, below) */
+       SQZ_FRAME_SHUFFLE = 4 };  /* flags: every block is byte-shuffled in front of the encoder (version 4, below) */
 struct sqz_frame_info {
     uint64_t content_bytes, payload_bytes, payload_off, frame_bytes, block_bytes;
     uint32_t n_blocks, win_bits, version, reserved;     /* reserved: the header's flags */
@@ -582,6 +583,96 @@ SQZ_API int sqz_frame_decompress_dict(const uint8_t* frame, uint64_t avail, cons
                                       uint8_t* data, uint64_t capacity, uint64_t* bytes, int32_t* block_err);
 SQZ_API int sqz_frame_read_dict(const uint8_t* frame, uint64_t avail, const uint8_t* dict, uint64_t dict_bytes,
                                 uint64_t offset, uint64_t length, uint8_t* out);
+
+/* SQZF version 4 = version 2's layout with flags bit 2 (SQZ_FRAME_SHUFFLE) and one 8-byte record directly behind the
+ * n index entries, the place and shape of version 3's:
+ *
+ *   4         1   version = 4.  A header is version 4 iff bit 2 of flags is set: version 4 without it or with any
+ *                 of bits 3..7, and versions 1 to 3 with bit 2, are EINVAL; so is bit 1 (SQZ_FRAME_DICT) together with
+ *                 bit 2, everywhere.  Bit 0 (SQZ_FRAME_STORED) may accompany it; a stored entry in a frame without
+ *                 bit 0 is EINVAL.
+ *   32 + 8n   4   elem_bytes    2, 4 or 8 (anything else EINVAL)
+ *   36 + 8n   4   zero          (anything else EINVAL)
+ *   ..            zero padding to the next multiple of 16 -> payload_off = pad16(32 + 8n + 8)
+ *
+ * index_crc covers bytes [0,28), the index and the record; the record's fields and the stored entries are looked at
+ * only once it has held.  With B a block of L bytes, e = elem_bytes and m = L / e rounded down, the block's stream is
+ * exactly the encoder's stream (greedy or lazy parse) for S, where
+ *     S[j * m + i] = B[i * e + j]    0 <= i < m, 0 <= j < e
+ * and the L - m * e tail bytes keep their place behind the planes.  content_crc is over B, the caller's bytes.  The
+ * stored rule is unchanged and exact, stored iff stream_bytes(S) >= L, and a stored block carries B, not S.  Blocks
+ * stay independent: ranged reads work as ever.  Empty content is a 48-byte frame.  A frame written without the
+ * filter is byte for byte what it always was.
+ * sqz_frame_info and sqz_frame_blocks accept version 4 (struct sqz_frame_info is unchanged: version = 4, reserved =
+ * flags); sqz_frame_elem reads the record (EINVAL for versions 1 to 3, E2BIG when avail does not cover it);
+ * sqz_frame_bound_shuf is the worst case of a frame written by sqz_frame_compress_shuf with the same flags
+ * (sqz_frame_bound_ex's for flags & SQZ_FRAME_STORED with the record's 8 bytes in front of the padding; 0 for any
+ * flag but SQZ_FRAME_STORED and SQZ_FRAME_SHUFFLE; sqz_frame_bound_ex and sqz_frame_bound_dict keep answering 0 for
+ * SQZ_FRAME_SHUFFLE).
+ * compress_shuf: flags 0 or SQZ_FRAME_STORED, with or without SQZ_FRAME_SHUFFLE, which is set in the header either
+ * way; EINVAL for any other flag (SQZ_FRAME_DICT among them), elem_bytes other than 2, 4, 8, a parse that is none.  It
+ * works in sqz_frame_compress's passes of whole blocks; a pass lies on the device once more, shuffled.
+ * decompress_shuf / read_shuf: sqz_frame_decompress / sqz_frame_read for frames of versions 1, 2 and 4 (EINVAL for
+ * version 3); the decoder's output of a pass lies in the scratch and the inverse shuffle writes the blocks that are
+ * not stored.  Every call there was keeps refusing a version-4 frame with EINVAL: sqz_frame_decompress,
+ * sqz_frame_read, the _dict readers, sqz_hip_frame_decode, sqz_hip_frame_read, and gather, update and append in both
+ * flavours (those three on version 4 are a later step).                                                          */
+SQZ_API int sqz_frame_elem(const uint8_t* frame, uint64_t avail, uint32_t* elem_bytes);
+SQZ_API uint64_t sqz_frame_bound_shuf(uint64_t content_bytes, uint32_t block_bits, uint32_t flags);
+SQZ_API int sqz_frame_compress_shuf(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                                    uint32_t flags, uint32_t parse, uint32_t elem_bytes, uint8_t* frame,
+                                    uint64_t capacity, uint64_t* frame_bytes);
+SQZ_API int sqz_frame_decompress_shuf(const uint8_t* frame, uint64_t avail, uint8_t* data, uint64_t capacity,
+                                      uint64_t* bytes, int32_t* block_err);
+SQZ_API int sqz_frame_read_shuf(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length, uint8_t* out);
+
+/* The byte shuffle on its own: n ragged ranges, range b = [d_off[b], d_off[b + 1]) of d_in and of d_out alike (d_off:
+ * n + 1 offsets in DEVICE memory), each transposed on its own as above (inverse != 0: back).  Any alignment of the
+ * pointers and offsets; d_in and d_out must not overlap; nothing outside a range is read or written.  Asynchronous
+ * on `stream`.  EINVAL: elem_bytes other than 2, 4, 8, a null pointer with n > 0, d_in == d_out.  Not among the
+ * kernels of sqz_hip_timing.                                                                                     */
+SQZ_API int sqz_hip_shuffle_blocks(const void* d_in, const uint64_t* d_off, uint32_t n, uint32_t elem_bytes,
+                                   int inverse, void* d_out, void* stream);
+
+/* Version 4 in the device-resident flavour.  Every pointer a DEVICE pointer (d_frame and d_scratch 16-byte aligned),
+ * asynchronous, no host synchronisation inside; d_frame_bytes, d_status, d_err as for the _dict calls below.
+ * Call-level EINVAL, before the device is touched: elem_bytes other than 2, 4, 8, a parse that is none, flags other
+ * than SQZ_FRAME_STORED and SQZ_FRAME_SHUFFLE, null or misaligned d_frame / d_scratch, a scratch smaller than the
+ * formula says.  Every refusal leaves the output untouched.
+ *
+ * encode_shuf: the content is shuffled into the scratch and goes through the block encoder from there; checksums
+ *   and stored blocks are taken from d_in.  The frame equals sqz_frame_compress_shuf's byte for byte and fits
+ *   sqz_frame_bound_shuf.  Scratch:
+ *       sqz_hip_frame_scratch_bytes_shuf(c, b, 1, flags) = sqz_hip_frame_scratch_bytes_ex(c, b, 1, flags & SQZ_FRAME_STORED)
+ *                                                          + round_up_256(c + 16)
+ *       sqz_hip_frame_scratch_bytes_shuf(c, b, 0, flags) = sqz_hip_frame_scratch_bytes(c, b, 0) + round_up_256(c + 16)
+ *   and 0 for a block_bits outside 12..24 or any other flag.
+ * decode_shuf: elem_bytes is what sqz_frame_elem said about a host copy of header, index and record; avail must
+ *   cover them, 32 + 8 n + 8 bytes (E2BIG at the call otherwise).  A kernel checks, in this order: magic, version 4
+ *   with flags bit 2 and none of bits 1, 3..7, field ranges (EINVAL; so a frame of versions 1 to 3 is EINVAL here);
+ *   the header against n_blocks and content_bytes (EINVAL); index_crc over [0,28), index and record (EILSEQ); the
+ *   record { 2 | 4 | 8, 0 } with the caller's elem_bytes (EINVAL); stored entries only with bit 0 and of their block's
+ *   size (EINVAL); the words' sum against payload_bytes (EINVAL); the payload inside avail (E2BIG).  On any of these
+ *   *d_status and every d_err[b] get that value and d_out is not written.  Otherwise the decoder writes into the
+ *   scratch, the inverse shuffle writes the blocks that are not stored into d_out, the stored ones are copied, and
+ *   checksums and d_err[b] are those of sqz_hip_frame_decode, over d_out.
+ * read_shuf: sqz_hip_frame_read for a version-4 frame, with elem_bytes as for decode_shuf.  Scratch:
+ *       sqz_hip_frame_read_scratch_bytes_shuf(length, b) = sqz_hip_frame_read_scratch_bytes(length, b)
+ *                                                          + round_up_256((k << b) + 16)
+ *       with k as there; 0 for a bad block_bits.                                                                 */
+SQZ_API uint64_t sqz_hip_frame_scratch_bytes_shuf(uint64_t content_bytes, uint32_t block_bits, int encode, uint32_t flags);
+SQZ_API int sqz_hip_frame_encode_shuf(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
+                                      uint32_t flags, uint32_t parse, uint32_t elem_bytes, void* d_frame,
+                                      uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err,
+                                      void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API int sqz_hip_frame_decode_shuf(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                      uint32_t elem_bytes, void* d_out, int32_t* d_err, int32_t* d_status,
+                                      void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API uint64_t sqz_hip_frame_read_scratch_bytes_shuf(uint64_t length, uint32_t block_bits);
+SQZ_API int sqz_hip_frame_read_shuf(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                                    uint32_t block_bits, uint32_t elem_bytes, uint64_t offset, uint64_t length,
+                                    void* d_out, int32_t* d_err, int32_t* d_status, void* d_scratch,
+                                    uint64_t scratch_bytes, void* stream);
 
 /* Version 3 in the device-resident flavour, and ranged reads from a frame that is already in device memory.  Every
  * pointer a DEVICE pointer (d_frame and d_scratch 16-byte aligned), asynchronous, no host synchronisation inside;

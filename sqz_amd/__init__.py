@@ -10,10 +10,10 @@ from .codec import (SqzError, bound, compress, decompress, device_info,  # noqa:
 
 __all__ = ["SqzError", "bound", "compress", "decompress", "device_info", "file_words",
            "MIN_WIN_BITS", "MAX_WIN_BITS", "compress_frame", "decompress_frame", "frame_info", "read_range",
-           "frame_blocks", "frame_bound", "gather_frame", "update_frame", "append_frame"]
+           "frame_blocks", "frame_bound", "gather_frame", "update_frame", "append_frame", "shuffle_blocks"]
 
 _FRAME = ("compress_frame", "decompress_frame", "frame_info", "read_range", "frame_blocks", "frame_bound", "gather_frame", "update_frame",
-          "append_frame")
+          "append_frame", "shuffle_blocks")
 
 
 def __getattr__(name):

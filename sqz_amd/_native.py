@@ -178,6 +178,21 @@ PROTOTYPES = {
                                      _vp, _vp, _vp, C.c_uint64, _vp]),
     "sqz_hip_frame_read_dict": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64,
                                           _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_frame_elem": (C.c_int, [_vp, C.c_uint64, _u32p]),
+    "sqz_frame_bound_shuf": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "sqz_frame_compress_shuf": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          _vp, C.c_uint64, _u64p]),
+    "sqz_frame_decompress_shuf": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _u64p, _vp]),
+    "sqz_frame_read_shuf": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp]),
+    "sqz_hip_shuffle_blocks": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_int, _vp, _vp]),
+    "sqz_hip_frame_scratch_bytes_shuf": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32]),
+    "sqz_hip_frame_encode_shuf": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_frame_decode_shuf": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp,
+                                            C.c_uint64, _vp]),
+    "sqz_hip_frame_read_scratch_bytes_shuf": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "sqz_hip_frame_read_shuf": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                          C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
     "sqz_hip_frame_gather_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "sqz_hip_frame_gather": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32,
                                        C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_uint64,

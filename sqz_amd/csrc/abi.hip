@@ -62,7 +62,7 @@ struct Lane {
     hipStream_t own = nullptr;      // created with the lane (non-blocking: independent of the NULL stream)
     int device = -1;                // hipGetDevice() when the lane was made: its buffers and stream live there
     DevBuf in, out, in_off, out_off, tokens, tok_count, out_bytes, err, end_bit, work_a, work_m,
-           dense, dense_off, crc, misc, dict, dict_idx, mask;
+           dense, dense_off, crc, misc, dict, dict_idx, mask, shuf;
     std::vector<uint8_t> host_dense;   // landing area of the host flavour's one device-to-host copy
 };
 
@@ -575,12 +575,15 @@ uint64_t frame_pass_blocks(uint64_t block_bytes) {
 
 // where the pieces of a device call's scratch lie (every piece 256-byte aligned)
 struct FrameScratch {
-    uint64_t in_off, out_off, out_bytes, copy_bytes, dense_off, crc, misc, slabs, codec, codec_bytes, stored, total;
+    uint64_t in_off, out_off, out_bytes, copy_bytes, dense_off, crc, misc, slabs, codec, codec_bytes, stored, shuf, total;
 };
 // store: an encode that may store blocks has a mask of its own.  A decode keeps its mask in `crc`: the open
 // kernel writes it, the decode and copy kernels read it, and only then, on the same stream, do the checksums
 // of the output land there -- so a decode of either version needs exactly the scratch it always did.
-FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_bytes, bool encode, bool store = false) {
+// shuf: version 4 keeps the shuffled content, round_up_256(content_bytes + 16) bytes, behind everything else -- an
+// encode the whole content before the encoder reads it, a decode the selected blocks as the decoder leaves them
+FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_bytes, bool encode, bool store = false,
+                           bool shuf = false) {
     FrameScratch L = {};
     uint64_t at = 0;
     auto take = [&at](uint64_t bytes) { const uint64_t r = at; at += align_up(bytes, 256); return r; };
@@ -601,6 +604,7 @@ FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_byt
     }
     L.codec = take(L.codec_bytes);
     L.stored = encode && store ? take(n * 4 + 4) : L.crc;
+    L.shuf = shuf ? take(content_bytes + 16) : 0;
     L.total = at;
     return L;
 }
@@ -609,13 +613,15 @@ FrameScratch frame_scratch(uint64_t n, uint64_t content_bytes, uint64_t slab_byt
 int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
                      uint8_t* d_frame, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
                      int32_t* d_err, uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t flags = 0,
-                     uint32_t parse = SQZ_PARSE_GREEDY, const uint8_t* d_dict = nullptr, uint32_t dict_bytes = 0) {
+                     uint32_t parse = SQZ_PARSE_GREEDY, const uint8_t* d_dict = nullptr, uint32_t dict_bytes = 0,
+                     uint32_t elem = 0) {
+    // elem: 2, 4 or 8 writes version 4 (never with a dictionary); 0 every other version as it always was
     const uint64_t bb = 1ull << block_bits, n64 = frame_blocks(content_bytes, block_bits);
     if (n64 > 0xFFFFFFFFull) { return EINVAL; }
     const uint32_t n = (uint32_t)n64;
     const uint64_t slab = sqz_bound(bb);
     const bool store = (flags & SQZ_FRAME_STORED) != 0;
-    const FrameScratch L = frame_scratch(n, content_bytes, slab, true, store);
+    const FrameScratch L = frame_scratch(n, content_bytes, slab, true, store, elem != 0);
     // version 3: the dictionary's index lies in front of everything else, as in sqz_hip_encode_blocks_dict
     const uint64_t dict_area = d_dict != nullptr ? dict_index_bytes(dict_bytes) : 0;
     if (scratch_bytes < dict_area + L.total) { return EINVAL; }
@@ -645,7 +651,12 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
         const uint64_t slots = (L.codec_bytes - head) / 8;
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + head);
-        run_encode(d_dict != nullptr ? 1 : finder_for(parse), d_in, in_off, n, 1u << win_bits, tokens, counts, tokens,
+        const uint8_t* enc_in = d_in;                       // version 4: the encoder reads every block shuffled; checksum
+        if (elem != 0) {                                    // (above) and stored blocks (below) keep to the caller's bytes
+            sqzk::launch_shuffle_blocks(d_in, in_off, n, elem, false, scratch + L.shuf, nullptr, bb, st);
+            enc_in = scratch + L.shuf;
+        }
+        run_encode(d_dict != nullptr ? 1 : finder_for(parse), enc_in, in_off, n, 1u << win_bits, tokens, counts, tokens,
                    tokens + slots, bb, scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st, parse,
                    d_dict != nullptr ? &dd : nullptr);
     }
@@ -654,6 +665,9 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
           sqzk::launch_frame_index_v3(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, flags, dict_bytes,
                                       dict_crc, d_frame, capacity, copy_bytes, dense_off, stored, idx_off,
                                       d_frame_bytes, d_status, st);
+      } else if (elem != 0) {
+          sqzk::launch_frame_index_v4(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, flags, elem, d_frame,
+                                      capacity, copy_bytes, dense_off, stored, idx_off, d_frame_bytes, d_status, st);
       } else if (store) {
           sqzk::launch_frame_index_v2(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, d_frame, capacity,
                                       copy_bytes, dense_off, stored, idx_off, d_frame_bytes, d_status, st);
@@ -661,7 +675,7 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
           sqzk::launch_frame_index(out_bytes, d_err, crc, n, content_bytes, win_bits, block_bits, d_frame, capacity,
                                    copy_bytes, dense_off, idx_off, d_frame_bytes, d_status, st);
       } }
-    const uint32_t record = d_dict != nullptr ? 8 : 0;
+    const uint32_t record = d_dict != nullptr || elem != 0 ? 8 : 0;
     { SpanGuard g(st, SQZ_HIP_K_CRC32);
       sqzk::launch_crc32_blocks(d_frame, idx_off, 1, idx_crc, 8 * (uint64_t)n + record, st); }
     sqzk::launch_frame_seal(d_frame, idx_crc, n, d_status, st, record);
@@ -682,13 +696,16 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
 void run_frame_decode(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* out_off, uint32_t n,
                       uint64_t size_hint, uint32_t* tokens, uint32_t* counts, uint8_t* d_out, int32_t* d_err,
                       const uint32_t* skip, const uint32_t* stored, uint32_t* crc, const DictDev& dd, hipStream_t st,
-                      uint32_t n_streams = 0) {
+                      uint32_t n_streams = 0, uint8_t* d_shuf = nullptr, uint32_t elem = 0) {
+    // d_shuf, elem: version 4 -- the expansion writes the shuffled blocks there (same offsets), the inverse shuffle
+    // brings every block that is not stored to d_out; stored blocks, checksums and verification then see d_out as ever
     // n_streams: how many of the n entries can be streams at all, where that is fewer (a gather's pseudo-blocks)
     { SpanGuard g(st, SQZ_HIP_K_ENTROPY_DECODE);
       sqzk::launch_entropy_decode(d_in, in_off, out_off, tokens, counts, d_err, nullptr, n, 0,
                                   decode_waves_for(n_streams != 0 ? n_streams : n), st, skip, dd.len); }
     { SpanGuard g(st, SQZ_HIP_K_LZ_EXPAND);
-      sqzk::launch_lz_expand(tokens, counts, d_out, out_off, n, st, skip, dd.bytes, dd.len); }
+      sqzk::launch_lz_expand(tokens, counts, d_shuf != nullptr ? d_shuf : d_out, out_off, n, st, skip, dd.bytes, dd.len); }
+    if (d_shuf != nullptr) { sqzk::launch_shuffle_blocks(d_shuf, out_off, n, elem, true, d_out, skip, size_hint, st); }
     if (skip != nullptr) {                                  // a stored block ignores the dictionary
         SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
         sqzk::launch_range_copy(d_in, in_off, d_out, out_off, out_off, stored, n, false, size_hint, st);
@@ -701,9 +718,11 @@ void run_frame_decode(const uint8_t* d_in, const uint64_t* in_off, const uint64_
 int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_t content_bytes, uint32_t first,
                      uint32_t n_sel, uint64_t sel_bytes, uint8_t* d_out, int32_t* d_err, int32_t* d_status,
                      uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, uint32_t version,
-                     const uint8_t* d_dict = nullptr, uint32_t dict_bytes = 0, uint32_t want_bits = 0) {
-    const FrameScratch L = frame_scratch(n_sel, sel_bytes, 0, false);
-    const uint64_t record = d_dict != nullptr ? 8 : 0;      // a dictionary: the version-3 reader, and no other
+                     const uint8_t* d_dict = nullptr, uint32_t dict_bytes = 0, uint32_t want_bits = 0,
+                     uint32_t elem = 0) {
+    // elem: 2, 4 or 8 is the version-4 reader, and no other (never with a dictionary)
+    const FrameScratch L = frame_scratch(n_sel, sel_bytes, 0, false, false, elem != 0);
+    const uint64_t record = d_dict != nullptr || elem != 0 ? 8 : 0;    // a dictionary: the version-3 reader, and no other
     if (scratch_bytes < L.total || avail < 32 + 8 * (uint64_t)n + record) { return scratch_bytes < L.total ? EINVAL : E2BIG; }
     uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
     uint64_t* out_off = (uint64_t*)(scratch + L.out_off);
@@ -729,6 +748,10 @@ int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_
         sqzk::launch_frame_open_v3(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, dict_bytes, dict_crc, in_off,
                                    out_off, stored, d_status, st, want_bits);
         dd.bytes = d_dict; dd.len = dict_bytes;
+    } else if (elem != 0) {
+        SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+        sqzk::launch_frame_open_v4(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, elem, in_off, out_off, stored,
+                                   d_status, st, want_bits);
     } else {
         SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
         sqzk::launch_frame_open_v2(d_frame, avail, n, content_bytes, first, n_sel, idx_crc, in_off, out_off, stored,
@@ -741,7 +764,7 @@ int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + align_up((uint64_t)n_sel * 4, 256));
         run_frame_decode(d_frame, in_off, out_off, n_sel, (sel_bytes + n_sel - 1) / n_sel, tokens, counts, d_out, d_err,
-                         skip, stored, crc, dd, st);
+                         skip, stored, crc, dd, st, 0, elem != 0 ? scratch + L.shuf : nullptr, elem);
         sqzk::launch_frame_verify(d_frame, first, n_sel, crc, d_status, d_err, st);
     }
     return hip_errno(hipGetLastError());
@@ -750,9 +773,9 @@ int frame_decode_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_
 // where the pieces of a ranged read's scratch lie: the decode's scratch for the covering blocks, the blocks
 // themselves, the copy's work list
 struct ReadScratch { FrameScratch dec; uint64_t blocks, plan, total; };
-ReadScratch read_scratch(uint64_t n_sel, uint64_t sel_bytes) {
+ReadScratch read_scratch(uint64_t n_sel, uint64_t sel_bytes, bool shuf = false) {
     ReadScratch R;
-    R.dec = frame_scratch(n_sel, sel_bytes, 0, false);
+    R.dec = frame_scratch(n_sel, sel_bytes, 0, false, false, shuf);
     R.blocks = R.dec.total;
     R.plan = R.blocks + align_up(sel_bytes + 16, 256);
     R.total = R.plan + 256;
@@ -764,17 +787,18 @@ ReadScratch read_scratch(uint64_t n_sel, uint64_t sel_bytes) {
 // the range against content_bytes and n against block_bits; length > 0
 int frame_read_dev(const uint8_t* d_frame, uint64_t avail, uint32_t n, uint64_t content_bytes, uint32_t block_bits,
                    uint64_t offset, uint64_t length, uint8_t* d_out, int32_t* d_err, int32_t* d_status,
-                   uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, const uint8_t* d_dict, uint32_t dict_bytes) {
+                   uint8_t* scratch, uint64_t scratch_bytes, hipStream_t st, const uint8_t* d_dict, uint32_t dict_bytes,
+                   uint32_t elem = 0) {
     const uint64_t bb = 1ull << block_bits;
     const uint64_t first = offset >> block_bits, b_end = ((offset + length - 1) >> block_bits) + 1;
     const uint64_t n_sel = b_end - first;
     const uint64_t sel_bytes = (b_end * bb < content_bytes ? b_end * bb : content_bytes) - first * bb;
-    const ReadScratch R = read_scratch(n_sel, sel_bytes);
+    const ReadScratch R = read_scratch(n_sel, sel_bytes, elem != 0);
     if (scratch_bytes < R.total) { return EINVAL; }
     uint8_t* const blocks = scratch + R.blocks;
     uint64_t* const plan = (uint64_t*)(scratch + R.plan);
     const int e = frame_decode_dev(d_frame, avail, n, content_bytes, (uint32_t)first, (uint32_t)n_sel, sel_bytes, blocks,
-                                   d_err, d_status, scratch, R.dec.total, st, 0, d_dict, dict_bytes, block_bits);
+                                   d_err, d_status, scratch, R.dec.total, st, 0, d_dict, dict_bytes, block_bits, elem);
     if (e != 0) { return e; }
     { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
       sqzk::launch_frame_read_plan(d_err, (uint32_t)n_sel, offset - first * bb, length, plan, d_status, st); }
@@ -791,6 +815,8 @@ template <class Sink>
 int frame_decode_host(Lane& c, hipStream_t st, const uint8_t* frame, const struct sqz_frame_info& fi,
                       uint64_t b_first, uint64_t b_end, Sink sink) {
     const uint64_t bb = fi.block_bytes, n = fi.n_blocks;
+    // version 4: the record's elem_bytes (sqz_frame_info has checked it), and a pass's scratch holds its blocks shuffled
+    const uint32_t elem = fi.version == 4 ? get_le32(frame + 32 + 8 * n) : 0u;
     std::vector<uint64_t> pre(n + 1);
     pre[0] = 0;
     for (uint64_t b = 0; b < n; b++) { pre[b + 1] = pre[b] + 8 * (uint64_t)frame_entry_words(frame, fi.version, b); }
@@ -803,7 +829,7 @@ int frame_decode_host(Lane& c, hipStream_t st, const uint8_t* frame, const struc
     for (uint64_t p0 = b_first; p0 < b_end; p0 += pass) {
         const uint64_t pn = b_end - p0 < pass ? b_end - p0 : pass;
         const uint64_t c0 = p0 * bb, c1 = (p0 + pn) * bb < fi.content_bytes ? (p0 + pn) * bb : fi.content_bytes;
-        const FrameScratch L = frame_scratch(pn, c1 - c0, 0, false);
+        const FrameScratch L = frame_scratch(pn, c1 - c0, 0, false, false, elem != 0);
         if ((e = c.out.reserve(c1 - c0 + 16)) || (e = c.work_a.reserve(L.total)) || (e = c.err.reserve(pn * 4))) { return e; }
         if (pre[p0 + pn] > pre[p0]) {
             HIP_TRY(hipMemcpyAsync(d_frame + fi.payload_off + pre[p0], frame + fi.payload_off + pre[p0],
@@ -811,7 +837,7 @@ int frame_decode_host(Lane& c, hipStream_t st, const uint8_t* frame, const struc
         }
         if ((e = frame_decode_dev(d_frame, fi.frame_bytes, (uint32_t)n, fi.content_bytes, (uint32_t)p0, (uint32_t)pn,
                                   c1 - c0, (uint8_t*)c.out.p, (int32_t*)c.err.p, (int32_t*)c.misc.p,
-                                  (uint8_t*)c.work_a.p, L.total, st, fi.version)) != 0) { return e; }
+                                  (uint8_t*)c.work_a.p, L.total, st, fi.version, nullptr, 0, 0, elem)) != 0) { return e; }
         errs.resize(pn);
         int32_t status = 0;
         HIP_TRY(hipMemcpyAsync(errs.data(), c.err.p, pn * 4, hipMemcpyDeviceToHost, st));
@@ -1586,12 +1612,15 @@ int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* 
     if (frame == NULL || out == NULL) { return EINVAL; }
     if (avail < 32) { return E2BIG; }
     const uint32_t win_bits = frame[5], block_bits = frame[6];
-    // version 1 has no flags; version 2 has at least one, and only known ones; version 3 iff SQZ_FRAME_DICT
+    // version 1 has no flags; version 2 has at least one, and only known ones; version 3 iff SQZ_FRAME_DICT;
+    // version 4 iff SQZ_FRAME_SHUFFLE (so never both)
     const uint32_t version = frame[4], flags = frame[7];
     const bool version_ok = (version == 1 && flags == 0) || (version == 2 && flags == (uint32_t)SQZ_FRAME_STORED) ||
                             (version == 3 && (flags & (uint32_t)SQZ_FRAME_DICT) != 0 &&
-                             (flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_DICT)) == 0);
-    const uint64_t record = version == 3 ? 8 : 0;           // { dict_bytes, dict_crc } behind the index
+                             (flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_DICT)) == 0) ||
+                            (version == 4 && (flags & (uint32_t)SQZ_FRAME_SHUFFLE) != 0 &&
+                             (flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_SHUFFLE)) == 0);
+    const uint64_t record = version >= 3 ? 8 : 0;           // { dict_bytes, dict_crc } or { elem_bytes, 0 } behind the index
     if (get_le32(frame) != 0x465A5153u || !version_ok || !frame_params_ok(win_bits, block_bits)) { return EINVAL; }
     const uint64_t content = get_le64(frame + 8), payload = get_le64(frame + 16);
     const uint64_t n = get_le32(frame + 24);
@@ -1613,6 +1642,10 @@ int sqz_frame_info(const uint8_t* frame, uint64_t avail, struct sqz_frame_info* 
         if (version == 3) {                                 // a dictionary of 1 .. window - 1 bytes
             const uint32_t db = get_le32(frame + 32 + 8 * n);
             if (db == 0 || db > (1u << win_bits) - 1u) { return EINVAL; }
+        }
+        if (version == 4) {                                 // elements of 2, 4 or 8 bytes, and a zero word
+            const uint32_t eb = get_le32(frame + 32 + 8 * n);
+            if ((eb != 2 && eb != 4 && eb != 8) || get_le32(frame + 32 + 8 * n + 4) != 0) { return EINVAL; }
         }
         uint64_t words = 0;
         for (uint64_t b = 0; b < n; b++) {                  // < 2^64: n, words < 2^32
@@ -1677,6 +1710,23 @@ int sqz_frame_dict(const uint8_t* frame, uint64_t avail, uint32_t* dict_bytes, u
     return 0;
 }
 
+uint64_t sqz_frame_bound_shuf(uint64_t content_bytes, uint32_t block_bits, uint32_t flags) {
+    if ((flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_SHUFFLE)) != 0) { return 0; }
+    const uint64_t plain = sqz_frame_bound_ex(content_bytes, block_bits, flags & (uint32_t)SQZ_FRAME_STORED);
+    if (plain == 0) { return 0; }
+    const uint64_t n = frame_blocks(content_bytes, block_bits);      // the record: 8 bytes more in front of the padding
+    return plain - frame_payload_off(n) + frame_payload_off(n, 8);
+}
+
+int sqz_frame_elem(const uint8_t* frame, uint64_t avail, uint32_t* elem_bytes) {
+    struct sqz_frame_info fi;
+    const int e = frame_check_host(frame, avail, &fi);
+    if (e != 0) { return e; }
+    if (fi.version != 4) { return EINVAL; }
+    if (elem_bytes != NULL) { *elem_bytes = get_le32(frame + 32 + 8 * (uint64_t)fi.n_blocks); }
+    return 0;
+}
+
 int sqz_frame_compress(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
                        uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
     return sqz_frame_compress_ex(data, bytes, win_bits, block_bits, 0, frame, capacity, frame_bytes);
@@ -1690,7 +1740,7 @@ int sqz_frame_compress_ex(const uint8_t* data, uint64_t bytes, uint32_t win_bits
 
 static int frame_compress_host(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
                                uint32_t flags, uint32_t parse, const uint8_t* dict, uint32_t dict_bytes,
-                               uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes);
+                               uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes, uint32_t elem = 0);
 
 int sqz_frame_compress_parse(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
                              uint32_t flags, uint32_t parse, uint8_t* frame, uint64_t capacity,
@@ -1707,17 +1757,29 @@ int sqz_frame_compress_dict(const uint8_t* data, uint64_t bytes, uint32_t win_bi
                                (uint32_t)dict_bytes, frame, capacity, frame_bytes);
 }
 
-// dict == NULL: versions 1 and 2 as they always were; else version 3, flags | SQZ_FRAME_DICT
+static bool elem_ok(uint32_t elem_bytes) { return elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8; }
+static bool frame_shuf_flags_ok(uint32_t flags) { return (flags & ~(uint32_t)(SQZ_FRAME_STORED | SQZ_FRAME_SHUFFLE)) == 0; }
+
+int sqz_frame_compress_shuf(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
+                            uint32_t flags, uint32_t parse, uint32_t elem_bytes, uint8_t* frame, uint64_t capacity,
+                            uint64_t* frame_bytes) {
+    if (!frame_shuf_flags_ok(flags) || !frame_params_ok(win_bits, block_bits) || !elem_ok(elem_bytes)) { return EINVAL; }
+    return frame_compress_host(data, bytes, win_bits, block_bits, flags & (uint32_t)SQZ_FRAME_STORED, parse, NULL, 0,
+                               frame, capacity, frame_bytes, elem_bytes);
+}
+
+// dict == NULL and elem == 0: versions 1 and 2 as they always were; a dictionary: version 3, flags | SQZ_FRAME_DICT;
+// elem 2, 4 or 8 (and no dictionary): version 4, flags | SQZ_FRAME_SHUFFLE
 static int frame_compress_host(const uint8_t* data, uint64_t bytes, uint32_t win_bits, uint32_t block_bits,
                                uint32_t flags, uint32_t parse, const uint8_t* dict, uint32_t dict_bytes,
-                               uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes) {
+                               uint8_t* frame, uint64_t capacity, uint64_t* frame_bytes, uint32_t elem) {
     if (!parse_ok(parse)) { return EINVAL; }
     if (frame_bytes == NULL || (frame == NULL && capacity > 0) || (data == NULL && bytes > 0) ||
         !frame_params_ok(win_bits, block_bits) || !frame_flags_ok(flags)) { return EINVAL; }
     const bool store = (flags & SQZ_FRAME_STORED) != 0;
     const uint64_t bb = 1ull << block_bits, n = frame_blocks(bytes, block_bits);
     if (n > 0xFFFFFFFFull) { return EINVAL; }
-    const uint64_t record = dict != NULL ? 8 : 0;
+    const uint64_t record = dict != NULL || elem != 0 ? 8 : 0;
     const uint64_t payload_off = frame_payload_off(n, record), slab = sqz_bound(bb);
     bool fits = capacity >= payload_off;
     std::vector<uint8_t> head(payload_off, 0);              // header, index, padding: built here, copied at the end
@@ -1746,7 +1808,14 @@ static int frame_compress_host(const uint8_t* data, uint64_t bytes, uint32_t win
             sqzk::launch_frame_plan(pn, bb, total_in, slab, (uint64_t*)c.in_off.p, (uint64_t*)c.out_off.p, st);
             { SpanGuard g(st, SQZ_HIP_K_CRC32);
               sqzk::launch_crc32_blocks((const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, (uint32_t*)c.crc.p, bb, st); }
-            run_encode(dict != NULL ? 1 : finder_for(parse), (const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn,
+            const uint8_t* enc_in = (const uint8_t*)c.in.p; // version 4: the encoder reads the pass shuffled, total_in + 16
+            if (elem != 0) {                                // bytes more on the device; checksums and stored blocks do not
+                if ((e = c.shuf.reserve(total_in + 16)) != 0) { return e; }
+                sqzk::launch_shuffle_blocks((const uint8_t*)c.in.p, (const uint64_t*)c.in_off.p, pn, elem, false,
+                                            (uint8_t*)c.shuf.p, nullptr, bb, st);
+                enc_in = (const uint8_t*)c.shuf.p;
+            }
+            run_encode(dict != NULL ? 1 : finder_for(parse), enc_in, (const uint64_t*)c.in_off.p, pn,
                        1u << win_bits,
                        (uint32_t*)c.work_a.p, (uint32_t*)c.tok_count.p, (uint32_t*)c.work_a.p, (uint32_t*)c.work_m.p, bb,
                        (uint8_t*)c.out.p, (const uint64_t*)c.out_off.p, (uint64_t*)c.out_bytes.p, (int32_t*)c.err.p,
@@ -1761,7 +1830,7 @@ static int frame_compress_host(const uint8_t* data, uint64_t bytes, uint32_t win
             bool any_stored = false;
             for (uint32_t b = 0; b < pn; b++) {
                 if (err[b] != 0) { return err[b]; }
-                if ((out_bytes[b] & 7u) != 0 || out_bytes[b] / 8 > (store ? 0x7FFFFFFFull : 0xFFFFFFFFull)) { return EINVAL; }
+                if ((out_bytes[b] & 7u) != 0 || out_bytes[b] / 8 > (store || elem != 0 ? 0x7FFFFFFFull : 0xFFFFFFFFull)) { return EINVAL; }
                 const uint64_t len = frame_block_len(bytes, block_bits, p0 + b);
                 const bool st_b = store && out_bytes[b] >= len;     // the writer's rule (include/sqz/sqz.h)
                 const uint64_t share = st_b ? align_up(len, 8) : out_bytes[b];
@@ -1798,8 +1867,8 @@ static int frame_compress_host(const uint8_t* data, uint64_t bytes, uint32_t win
     if (!fits) { return E2BIG; }
     uint8_t* h = head.data();
     put_le32(h, 0x465A5153u);
-    h[4] = dict != NULL ? 3 : store ? 2 : 1; h[5] = (uint8_t)win_bits; h[6] = (uint8_t)block_bits;
-    h[7] = (uint8_t)(flags | (dict != NULL ? (uint32_t)SQZ_FRAME_DICT : 0u));
+    h[4] = elem != 0 ? 4 : dict != NULL ? 3 : store ? 2 : 1; h[5] = (uint8_t)win_bits; h[6] = (uint8_t)block_bits;
+    h[7] = (uint8_t)(flags | (dict != NULL ? (uint32_t)SQZ_FRAME_DICT : 0u) | (elem != 0 ? (uint32_t)SQZ_FRAME_SHUFFLE : 0u));
     put_le64(h + 8, bytes);
     put_le64(h + 16, payload);
     put_le32(h + 24, (uint32_t)n);
@@ -1807,17 +1876,40 @@ static int frame_compress_host(const uint8_t* data, uint64_t bytes, uint32_t win
         put_le32(h + 32 + 8 * n, dict_bytes);
         put_le32(h + 32 + 8 * n + 4, host_crc32(0, dict, dict_bytes));
     }
+    if (elem != 0) { put_le32(h + 32 + 8 * n, elem); }      // the record: { elem_bytes, 0 }
     put_le32(h + 28, host_crc32(host_crc32(0, h, 28), h + 32, 8 * n + record));
     memcpy(frame, h, payload_off);
     return 0;
 }
 
+// most_version: 2 for the calls there always were, 4 for the _shuf readers, which take versions 1, 2 and 4
+static int frame_decompress_host(const uint8_t* frame, uint64_t avail, uint8_t* data, uint64_t capacity,
+                                 uint64_t* bytes, int32_t* block_err, uint32_t most_version);
+static int frame_read_host(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length, uint8_t* out,
+                           uint32_t most_version);
+
 int sqz_frame_decompress(const uint8_t* frame, uint64_t avail, uint8_t* data, uint64_t capacity,
                          uint64_t* bytes, int32_t* block_err) {
+    return frame_decompress_host(frame, avail, data, capacity, bytes, block_err, 2);
+}
+int sqz_frame_decompress_shuf(const uint8_t* frame, uint64_t avail, uint8_t* data, uint64_t capacity,
+                              uint64_t* bytes, int32_t* block_err) {
+    return frame_decompress_host(frame, avail, data, capacity, bytes, block_err, 4);
+}
+int sqz_frame_read(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length, uint8_t* out) {
+    return frame_read_host(frame, avail, offset, length, out, 2);
+}
+int sqz_frame_read_shuf(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length, uint8_t* out) {
+    return frame_read_host(frame, avail, offset, length, out, 4);
+}
+
+static int frame_decompress_host(const uint8_t* frame, uint64_t avail, uint8_t* data, uint64_t capacity,
+                                 uint64_t* bytes, int32_t* block_err, uint32_t most_version) {
     struct sqz_frame_info fi;
     int e = frame_check_host(frame, avail, &fi);
     if (e != 0) { return e; }
-    if (fi.version == 3) { return EINVAL; }                 // needs its dictionary: sqz_frame_decompress_dict
+    // version 3 needs its dictionary: sqz_frame_decompress_dict; version 4 its inverse shuffle: sqz_frame_decompress_shuf
+    if (fi.version == 3 || fi.version > most_version) { return EINVAL; }
     if (bytes != NULL) { *bytes = fi.content_bytes; }
     if (avail < fi.frame_bytes || capacity < fi.content_bytes) { return E2BIG; }
     if (fi.n_blocks == 0) { return 0; }
@@ -1840,11 +1932,12 @@ int sqz_frame_decompress(const uint8_t* frame, uint64_t avail, uint8_t* data, ui
     return e != 0 ? e : first_bad;
 }
 
-int sqz_frame_read(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length, uint8_t* out) {
+static int frame_read_host(const uint8_t* frame, uint64_t avail, uint64_t offset, uint64_t length, uint8_t* out,
+                           uint32_t most_version) {
     struct sqz_frame_info fi;
     int e = frame_check_host(frame, avail, &fi);
     if (e != 0) { return e; }
-    if (fi.version == 3) { return EINVAL; }                 // needs its dictionary: sqz_frame_read_dict
+    if (fi.version == 3 || fi.version > most_version) { return EINVAL; }   // sqz_frame_read_dict, sqz_frame_read_shuf
     if (offset > fi.content_bytes || length > fi.content_bytes - offset || (out == NULL && length > 0)) { return EINVAL; }
     if (length == 0) { return 0; }
     const uint64_t bb = fi.block_bytes, b_first = offset / bb, b_end = (offset + length - 1) / bb + 1;
@@ -2055,7 +2148,7 @@ uint64_t sqz_hip_frame_read_scratch_bytes(uint64_t length, uint32_t block_bits) 
 static int frame_read_call(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
                            uint32_t block_bits, uint64_t offset, uint64_t length, const void* d_dict,
                            uint64_t dict_bytes, void* d_out, int32_t* d_err, int32_t* d_status, void* d_scratch,
-                           uint64_t scratch_bytes, void* stream) {
+                           uint64_t scratch_bytes, void* stream, uint32_t elem = 0) {
     if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
         frame_blocks(content_bytes, block_bits) != n_blocks || offset > content_bytes ||
         length > content_bytes - offset) { return EINVAL; }
@@ -2066,7 +2159,7 @@ static int frame_read_call(const void* d_frame, uint64_t avail, uint32_t n_block
     if (length == 0) { return hip_errno(hipMemsetAsync(d_status, 0, 4, (hipStream_t)stream)); }
     return frame_read_dev((const uint8_t*)d_frame, avail, n_blocks, content_bytes, block_bits, offset, length,
                           (uint8_t*)d_out, d_err, d_status, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
-                          (const uint8_t*)d_dict, (uint32_t)dict_bytes);
+                          (const uint8_t*)d_dict, (uint32_t)dict_bytes, elem);
 }
 
 int sqz_hip_frame_read(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
@@ -2083,6 +2176,69 @@ int sqz_hip_frame_read_dict(const void* d_frame, uint64_t avail, uint32_t n_bloc
     if (!dict_ok(d_dict, dict_bytes, (uint32_t)sqzk_max_window)) { return EINVAL; }
     return frame_read_call(d_frame, avail, n_blocks, content_bytes, block_bits, offset, length, d_dict, dict_bytes,
                            d_out, d_err, d_status, d_scratch, scratch_bytes, stream);
+}
+
+// ---- version 4 in the device-resident flavour
+// encode: sqz_hip_frame_scratch_bytes_ex(c, b, 1, flags & SQZ_FRAME_STORED) + round_up_256(c + 16), the shuffled content;
+// decode: sqz_hip_frame_scratch_bytes(c, b, 0) + round_up_256(c + 16), the blocks as the decoder leaves them
+uint64_t sqz_hip_frame_scratch_bytes_shuf(uint64_t content_bytes, uint32_t block_bits, int encode, uint32_t flags) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        !frame_shuf_flags_ok(flags) || content_bytes > ~(uint64_t)0 / 16) { return 0; }
+    const uint64_t n = frame_blocks(content_bytes, block_bits);
+    return frame_scratch(n, content_bytes, sqz_bound(1ull << block_bits), encode != 0,
+                         encode != 0 && (flags & SQZ_FRAME_STORED) != 0, true).total;
+}
+
+int sqz_hip_frame_encode_shuf(const void* d_in, uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits,
+                              uint32_t flags, uint32_t parse, uint32_t elem_bytes, void* d_frame, uint64_t capacity,
+                              uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err, void* d_scratch,
+                              uint64_t scratch_bytes, void* stream) {
+    if (!parse_ok(parse) || !frame_shuf_flags_ok(flags) || !frame_params_ok(win_bits, block_bits) ||
+        !elem_ok(elem_bytes)) { return EINVAL; }
+    if ((d_in == NULL && content_bytes > 0) || d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 ||
+        d_frame_bytes == NULL || d_status == NULL || (d_err == NULL && content_bytes > 0) || d_scratch == NULL ||
+        ((uintptr_t)d_scratch & 15u) != 0 ||
+        scratch_bytes < sqz_hip_frame_scratch_bytes_shuf(content_bytes, block_bits, 1, flags)) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    return frame_encode_dev((const uint8_t*)d_in, content_bytes, win_bits, block_bits, (uint8_t*)d_frame, capacity,
+                            d_frame_bytes, d_status, d_err, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
+                            flags & (uint32_t)SQZ_FRAME_STORED, parse, nullptr, 0, elem_bytes);
+}
+
+int sqz_hip_frame_decode_shuf(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                              uint32_t elem_bytes, void* d_out, int32_t* d_err, int32_t* d_status, void* d_scratch,
+                              uint64_t scratch_bytes, void* stream) {
+    if (!elem_ok(elem_bytes)) { return EINVAL; }
+    if (d_frame == NULL || ((uintptr_t)d_frame & 15u) != 0 || d_status == NULL || d_scratch == NULL ||
+        ((uintptr_t)d_scratch & 15u) != 0 || (n_blocks > 0 && (d_out == NULL || d_err == NULL)) ||
+        (n_blocks == 0) != (content_bytes == 0) || content_bytes / (1ull << sqz_frame_min_block_bits) + 1 < n_blocks) {
+        return EINVAL;
+    }
+    if (scratch_bytes < frame_scratch(n_blocks, content_bytes, 0, false, false, true).total) { return EINVAL; }
+    if (avail < 32 + 8 * (uint64_t)n_blocks + 8) { return E2BIG; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    return frame_decode_dev((const uint8_t*)d_frame, avail, n_blocks, content_bytes, 0, n_blocks, content_bytes,
+                            (uint8_t*)d_out, d_err, d_status, (uint8_t*)d_scratch, scratch_bytes, (hipStream_t)stream,
+                            0, nullptr, 0, 0, elem_bytes);
+}
+
+// sqz_hip_frame_read_scratch_bytes(length, b) + round_up_256((k << b) + 16): the covering blocks once more, shuffled
+uint64_t sqz_hip_frame_read_scratch_bytes_shuf(uint64_t length, uint32_t block_bits) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits) { return 0; }
+    const uint64_t bb = 1ull << block_bits;
+    if (length > ~(uint64_t)0 / 16 - 2 * bb) { return 0; }
+    const uint64_t n = length == 0 ? 0 : ((length + bb - 2) >> block_bits) + 1;
+    return read_scratch(n, n * bb, true).total;
+}
+
+int sqz_hip_frame_read_shuf(const void* d_frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                            uint32_t block_bits, uint32_t elem_bytes, uint64_t offset, uint64_t length, void* d_out,
+                            int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!elem_ok(elem_bytes)) { return EINVAL; }
+    return frame_read_call(d_frame, avail, n_blocks, content_bytes, block_bits, offset, length, NULL, 0, d_out, d_err,
+                           d_status, d_scratch, scratch_bytes, stream, elem_bytes);
 }
 
 // ---- many ranges of a resident frame in one call
@@ -2636,6 +2792,18 @@ int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n,
     if (e != 0) { return e; }
     SpanGuard g((hipStream_t)stream, SQZ_HIP_K_CRC32);
     sqzk::launch_crc32_blocks((const uint8_t*)d_in, d_in_off, n, d_crc, 0, (hipStream_t)stream);
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_shuffle_blocks(const void* d_in, const uint64_t* d_off, uint32_t n, uint32_t elem_bytes, int inverse,
+                           void* d_out, void* stream) {
+    if (!elem_ok(elem_bytes)) { return EINVAL; }
+    if (n == 0) { return 0; }
+    if (d_in == NULL || d_off == NULL || d_out == NULL || d_in == d_out) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    sqzk::launch_shuffle_blocks((const uint8_t*)d_in, d_off, n, elem_bytes, inverse != 0, (uint8_t*)d_out, nullptr, 0,
+                                (hipStream_t)stream);
     return hip_errno(hipGetLastError());
 }
 

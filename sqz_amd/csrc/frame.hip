@@ -119,6 +119,7 @@ __device__ __forceinline__ uint32_t crc32_small(const uint8_t* p, uint32_t n) {
 // SQZF version 2 (include/sqz/sqz.h): flags bit 0, bit 31 of an index entry's first word
 constexpr uint32_t kFrameStored = 1u;
 constexpr uint32_t kFrameDict = 2u;                // version 3: flags bit 1, and the record behind the index
+constexpr uint32_t kFrameShuffle = 4u;             // version 4: flags bit 2, and the record behind the index
 constexpr uint32_t kStoredBit = 0x80000000u;
 
 // content bytes of block b
@@ -276,7 +277,10 @@ void launch_frame_plan(uint32_t n_blocks, uint64_t block_bytes, uint64_t content
 // *dict_crc } directly behind the n entries, payload_off = pad16(32 + 8n + 8) -- the padding now falls on even n --
 // and idx_off = {32, 32 + 8n + 8}, so that the index checksum covers the record.  dict_crc is read on the device:
 // crc32_blocks_kernel over the dictionary wrote it earlier on the same stream.
-template <bool kDict>
+//
+// kShuf (flags has SQZ_FRAME_SHUFFLE, with or without SQZ_FRAME_STORED; never with kDict) writes version 4: the same
+// place and shape, the record being { elem_bytes, 0 } -- elem_bytes comes in dict_bytes' place, dict_crc is not read.
+template <bool kDict, bool kShuf = false>
 __device__ __forceinline__
 void frame_index_body(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
                       const uint32_t* __restrict__ crc, uint32_t n_blocks, uint64_t content_bytes,
@@ -294,8 +298,8 @@ void frame_index_body(const uint64_t* __restrict__ out_bytes, const int32_t* __r
     const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
     const bool store = (flags & kFrameStored) != 0;
     const uint64_t bb = 1ull << block_bits;
-    const uint64_t most_words = store || kDict ? 0x7FFFFFFFull : 0xFFFFFFFFull;    // bit 31 of the entry is the stored bit
-    const uint64_t record = kDict ? 8 : 0;
+    const uint64_t most_words = store || kDict || kShuf ? 0x7FFFFFFFull : 0xFFFFFFFFull;    // bit 31 of the entry is the stored bit
+    const uint64_t record = kDict || kShuf ? 8 : 0;
     uint64_t sum = 0;
     int32_t bad = 0;
     for (uint64_t b = b0; b < b1; b++) {
@@ -327,7 +331,7 @@ void frame_index_body(const uint64_t* __restrict__ out_bytes, const int32_t* __r
         if (st == 0) {
             uint32_t* const h = reinterpret_cast<uint32_t*>(frame);
             h[0] = 0x465A5153u;                                    // "SQZF"
-            h[1] = (kDict ? 3u : store ? 2u : 1u) | (win_bits << 8) | (block_bits << 16) | ((flags & 0xFFu) << 24);
+            h[1] = (kShuf ? 4u : kDict ? 3u : store ? 2u : 1u) | (win_bits << 8) | (block_bits << 16) | ((flags & 0xFFu) << 24);
                                                                    // version, win_bits, block_bits, flags
             h[2] = (uint32_t)content_bytes; h[3] = (uint32_t)(content_bytes >> 32);
             h[4] = (uint32_t)run; h[5] = (uint32_t)(run >> 32);
@@ -336,6 +340,9 @@ void frame_index_body(const uint64_t* __restrict__ out_bytes, const int32_t* __r
             uint32_t* const behind = h + 8 + 2 * (uint64_t)n_blocks;       // what follows the n entries
             if (kDict) {
                 behind[0] = dict_bytes; behind[1] = *dict_crc;
+                if ((n_blocks & 1u) == 0) { behind[2] = 0u; behind[3] = 0u; }
+            } else if (kShuf) {
+                behind[0] = dict_bytes; behind[1] = 0u;
                 if ((n_blocks & 1u) == 0) { behind[2] = 0u; behind[3] = 0u; }
             } else if ((n_blocks & 1u) != 0) { behind[0] = 0u; behind[1] = 0u; }
         }
@@ -382,6 +389,19 @@ void frame_index_v3_kernel(const uint64_t* __restrict__ out_bytes, const int32_t
                            dict_crc);
 }
 
+__global__ __launch_bounds__(256)
+void frame_index_v4_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
+                           const uint32_t* __restrict__ crc, uint32_t n_blocks, uint64_t content_bytes,
+                           uint32_t win_bits, uint32_t block_bits, uint8_t* __restrict__ frame, uint64_t capacity,
+                           uint64_t* __restrict__ copy_bytes, uint64_t* __restrict__ dense_off,
+                           uint64_t* __restrict__ idx_off, uint64_t* __restrict__ frame_bytes_out,
+                           int32_t* __restrict__ status_out, uint32_t flags, uint32_t* __restrict__ stored,
+                           uint32_t elem_bytes) {
+    frame_index_body<false, true>(out_bytes, err, crc, n_blocks, content_bytes, win_bits, block_bits, frame, capacity,
+                                  copy_bytes, dense_off, idx_off, frame_bytes_out, status_out, flags, stored,
+                                  elem_bytes, nullptr);
+}
+
 void launch_frame_index(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
                         uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint8_t* frame,
                         uint64_t capacity, uint64_t* copy_bytes, uint64_t* dense_off, uint64_t* idx_off,
@@ -408,6 +428,16 @@ void launch_frame_index_v3(const uint64_t* out_bytes, const int32_t* err, const 
     hipLaunchKernelGGL(frame_index_v3_kernel, dim3(1), dim3(256), 0, stream, out_bytes, err, crc, n_blocks,
                        content_bytes, win_bits, block_bits, frame, capacity, copy_bytes, dense_off, idx_off,
                        frame_bytes_out, status_out, (flags & kFrameStored) | kFrameDict, stored, dict_bytes, dict_crc);
+}
+
+void launch_frame_index_v4(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
+                           uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint32_t flags,
+                           uint32_t elem_bytes, uint8_t* frame, uint64_t capacity, uint64_t* copy_bytes,
+                           uint64_t* dense_off, uint32_t* stored, uint64_t* idx_off, uint64_t* frame_bytes_out,
+                           int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_index_v4_kernel, dim3(1), dim3(256), 0, stream, out_bytes, err, crc, n_blocks,
+                       content_bytes, win_bits, block_bits, frame, capacity, copy_bytes, dense_off, idx_off,
+                       frame_bytes_out, status_out, (flags & kFrameStored) | kFrameShuffle, stored, elem_bytes);
 }
 
 // index_crc = crc32(header[0, 28) || index): the header's 28 bytes on the spot, joined with the index's
@@ -462,7 +492,12 @@ void launch_frame_seal(uint8_t* frame, const uint32_t* idx_crc, uint32_t n_block
 // consecutive slots, so it lies in one piece.  *status_out = the frame's status, else ctl[1]; *blocks_decoded = 0
 // for a refused frame, else ctl[0].  With any status every one of the 2 * max_blocks entries is empty and skipped,
 // as are the entries behind slot ctl[0] otherwise: the launch behind this one is sized for max_blocks on the host.
-template <bool kDict, bool kList = false>
+//
+// kShuf is the reader of version 4, and of nothing else (never with kDict or kList).  idx_crc covers index and record
+// as for version 3; dict_bytes is the elem_bytes the caller read from its copy of the record, dict_crc is not read.
+// Its checks in the host's order: as above up to index_crc, then a record that is not { 2 | 4 | 8, 0 } or whose
+// elem_bytes is not the caller's EINVAL, then the stored entries and what follows them.
+template <bool kDict, bool kList = false, bool kShuf = false>
 __device__ __forceinline__
 void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
                      uint64_t content_bytes, uint32_t first, uint32_t n_sel,
@@ -481,7 +516,7 @@ void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t
     const int lane = (int)(t & 63u);
     if (t < 64) {                                  // wave 0, all of it: what index_crc has to be
         const uint32_t h = crc32_small(frame, 28);
-        const uint32_t c = gf_mul(h, xpow8_wave(8 * (uint64_t)n_blocks + (kDict ? 8 : 0), lane)) ^ *idx_crc;
+        const uint32_t c = gf_mul(h, xpow8_wave(8 * (uint64_t)n_blocks + (kDict || kShuf ? 8 : 0), lane)) ^ *idx_crc;
         if (lane == 0) { want_crc = c; }
     }
     const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
@@ -489,8 +524,8 @@ void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t
     const uint64_t b0 = t * per < n_blocks ? t * per : n_blocks;
     const uint64_t b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
     const uint32_t block_bits = frame[6];
-    const bool v2 = kDict ? frame[4] == 3 : frame[4] == 2;         // an entry's bit 31 is the stored bit
-    const bool may_store = !kDict || (frame[7] & kFrameStored) != 0;       // version 3 has the bit with or without the flag
+    const bool v2 = kShuf ? frame[4] == 4 : kDict ? frame[4] == 3 : frame[4] == 2;         // an entry's bit 31 is the stored bit
+    const bool may_store = !(kDict || kShuf) || (frame[7] & kFrameStored) != 0;    // versions 3 and 4 have the bit with or without the flag
     const uint32_t words_mask = v2 ? ~kStoredBit : 0xFFFFFFFFu;
     uint64_t sum = 0;
     uint32_t misfit = 0;                           // a stored entry whose size is not its block's, or in a frame without any
@@ -504,7 +539,7 @@ void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t
     sums[t] = sum;
     wrong[t] = misfit;
     __syncthreads();
-    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + (kDict ? 8 : 0) + 15) & ~(uint64_t)15;
+    const uint64_t payload_off = (32 + 8 * (uint64_t)n_blocks + (kDict || kShuf ? 8 : 0) + 15) & ~(uint64_t)15;
     if (t == 0) {
         uint64_t run = 0;
         bool beyond = false;                       // the streams add up to more than there is: stop adding (no wrap)
@@ -519,7 +554,9 @@ void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t
         const uint32_t win_bits = frame[5];
         // version 1 has no flags; version 2 has some, all of them known, and needs somewhere to put the mask;
         // version 3 has bit 1, perhaps bit 0, no other, and needs the mask as well
-        const bool version_ok = kDict ? frame[4] == 3 && (frame[7] & kFrameDict) != 0 &&
+        const bool version_ok = kShuf ? frame[4] == 4 && (frame[7] & kFrameShuffle) != 0 &&
+                                        (frame[7] & ~(kFrameStored | kFrameShuffle)) == 0 && (stored != nullptr || n_sel == 0)
+                              : kDict ? frame[4] == 3 && (frame[7] & kFrameDict) != 0 &&
                                         (frame[7] & ~(kFrameStored | kFrameDict)) == 0 && (stored != nullptr || n_sel == 0)
                                       : (frame[4] == 1 && frame[7] == 0) ||
                                         (frame[4] == 2 && frame[7] == kFrameStored && (stored != nullptr || n_sel == 0));
@@ -536,6 +573,9 @@ void frame_open_body(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t
             } else if (load_le32(frame + 28) != want_crc) {
                 st = kErrEILSEQ;
             } else if (kDict && (load_le32(rec) == 0 || load_le32(rec) > (1u << win_bits) - 1u)) {
+                st = kErrEINVAL;
+            } else if (kShuf && ((load_le32(rec) != 2u && load_le32(rec) != 4u && load_le32(rec) != 8u) ||
+                                 load_le32(rec + 4) != 0u || load_le32(rec) != dict_bytes)) {
                 st = kErrEINVAL;
             } else if (any_misfit != 0) {
                 st = kErrEINVAL;
@@ -639,6 +679,16 @@ void frame_open_v3_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uin
                           stored, dict_bytes, dict_crc, want_bits);
 }
 
+__global__ __launch_bounds__(256)
+void frame_open_v4_kernel(const uint8_t* __restrict__ frame, uint64_t avail, uint32_t n_blocks,
+                          uint64_t content_bytes, uint32_t first, uint32_t n_sel,
+                          const uint32_t* __restrict__ idx_crc, uint64_t* __restrict__ in_off,
+                          uint64_t* __restrict__ out_off, int32_t* __restrict__ status_out,
+                          uint32_t* __restrict__ stored, uint32_t elem_bytes, uint32_t want_bits) {
+    frame_open_body<false, false, true>(frame, avail, n_blocks, content_bytes, first, n_sel, idx_crc, in_off, out_off,
+                                        status_out, stored, elem_bytes, nullptr, want_bits);
+}
+
 void launch_frame_open(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
                        uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint64_t* in_off,
                        uint64_t* out_off, int32_t* status_out, hipStream_t stream) {
@@ -660,6 +710,14 @@ void launch_frame_open_v3(const uint8_t* frame, uint64_t avail, uint32_t n_block
                           int32_t* status_out, hipStream_t stream, uint32_t want_bits) {
     hipLaunchKernelGGL(frame_open_v3_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
                        first, n_sel, idx_crc, in_off, out_off, status_out, stored, dict_bytes, dict_crc, want_bits);
+}
+
+void launch_frame_open_v4(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                          uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint32_t elem_bytes,
+                          uint64_t* in_off, uint64_t* out_off, uint32_t* stored, int32_t* status_out,
+                          hipStream_t stream, uint32_t want_bits) {
+    hipLaunchKernelGGL(frame_open_v4_kernel, dim3(1), dim3(256), 0, stream, frame, avail, n_blocks, content_bytes,
+                       first, n_sel, idx_crc, in_off, out_off, status_out, stored, elem_bytes, want_bits);
 }
 
 __global__ __launch_bounds__(256)

@@ -138,6 +138,26 @@ void launch_frame_open_v3(const uint8_t* frame, uint64_t avail, uint32_t n_block
                           uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint32_t dict_bytes,
                           const uint32_t* dict_crc, uint64_t* in_off, uint64_t* out_off, uint32_t* stored,
                           int32_t* status_out, hipStream_t stream, uint32_t want_bits = 0);
+// version 4 (SQZ_FRAME_SHUFFLE, with or without SQZ_FRAME_STORED in `flags`): kernels of their own over the same code.
+// index: the record { elem_bytes, 0 } behind the entries, idx_off = {32, 32 + 8n + 8}; launch_frame_seal takes
+// record_bytes = 8.  open: idx_crc covers frame[32, 32 + 8n + 8); only a version-4 frame passes (EINVAL for versions
+// 1 to 3), and once index_crc has held its record must be { 2 | 4 | 8, 0 } and its first word the caller's
+// elem_bytes (EINVAL).  stored, want_bits: as for _v3
+void launch_frame_index_v4(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc, uint32_t n_blocks,
+                           uint64_t content_bytes, uint32_t win_bits, uint32_t block_bits, uint32_t flags,
+                           uint32_t elem_bytes, uint8_t* frame, uint64_t capacity, uint64_t* copy_bytes,
+                           uint64_t* dense_off, uint32_t* stored, uint64_t* idx_off, uint64_t* frame_bytes_out,
+                           int32_t* status_out, hipStream_t stream);
+void launch_frame_open_v4(const uint8_t* frame, uint64_t avail, uint32_t n_blocks, uint64_t content_bytes,
+                          uint32_t first, uint32_t n_sel, const uint32_t* idx_crc, uint32_t elem_bytes,
+                          uint64_t* in_off, uint64_t* out_off, uint32_t* stored, int32_t* status_out,
+                          hipStream_t stream, uint32_t want_bits = 0);
+// the byte shuffle of version 4 (shuffle.hip): range b = [off[b], off[b + 1]) of src and of dst alike; forward
+// dst[j * m + i] = src[i * e + j] with e = elem_bytes (2, 4 or 8; anything else launches nothing) and m = length / e,
+// the length % e tail bytes copied; inverse the other way.  Any alignment; src and dst must not overlap; ranges
+// with skip[b] != 0 are left alone (null: none).  size_hint as for launch_crc32_blocks
+void launch_shuffle_blocks(const uint8_t* src, const uint64_t* off, uint32_t n_ranges, uint32_t elem_bytes,
+                           bool inverse, uint8_t* dst, const uint32_t* skip, uint64_t size_hint, hipStream_t stream);
 // a ranged read's last step but one: *status = the frame's status, else the first non-zero err[0 .. n_sel); and the
 // one-range work list of launch_range_copy(src, plan, dst, plan + 2, plan + 2, (uint32_t*)(plan + 4), 1, ..):
 // `length` bytes from src + src_at to dst, masked out unless *status == 0.  plan: 5 x uint64

@@ -3,7 +3,8 @@
 Host flavour (bytes in, bytes out) and a device flavour over torch tensors in the style of batch.py.
 Every byte of codec and checksum work happens in libsqz_amd.so; nothing is computed here.
 
-    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18] [--store] [--lazy] [--dict FILE]   compress a file
+    python -m sqz_amd.frame c IN OUT [--win-bits 15] [--block-bits 18] [--store] [--lazy] [--dict FILE] [--shuffle N]
+                                                                           compress a file
     python -m sqz_amd.frame d IN OUT [--dict FILE]                         decompress one
     python -m sqz_amd.frame a FRAME IN OUT [--lazy] [--dict FILE]          append IN's bytes to FRAME (append_frame)
     python -m sqz_amd.frame info IN                                        describe one
@@ -16,6 +17,10 @@ dictionary=bytes / --dict FILE writes version 3: every block may reach back into
 bytes) as if it stood in front of the block.  The frame records the dictionary's length and CRC-32, not the
 dictionary: the reader brings the same bytes (anything else is EILSEQ).  For frames of small blocks of text; it can
 make an executable larger (README).
+shuffle=2|4|8 / --shuffle N writes version 4: every block is byte-shuffled in front of the encoder -- all first bytes
+of its N-byte elements, then all second bytes, and so on -- which is what arrays of numbers want (README has the
+figures; noise gains nothing and a few inputs lose a little, so it is opt-in).  The readers pick the version up from
+the header.  Not together with a dictionary; gather, update and append do not take version 4 yet.
 """
 import ctypes as C
 import errno
@@ -26,14 +31,37 @@ from .codec import MAX_DICT_BYTES, PARSE_LAZY, SqzError, _raise, dict_bytes, par
 HEADER_BYTES = 32
 FRAME_STORED = 1            # SQZ_FRAME_STORED
 FRAME_DICT = 2              # SQZ_FRAME_DICT
+FRAME_SHUFFLE = 4           # SQZ_FRAME_SHUFFLE
+
+
+def shuffle_code(shuffle) -> int:
+    """shuffle= as the element size of a version-4 frame: 0 (none), 2, 4 or 8; anything else is ValueError"""
+    if isinstance(shuffle, bool) or shuffle not in (0, 2, 4, 8):
+        raise ValueError(f"shuffle must be 0, 2, 4 or 8, not {shuffle!r}")
+    return int(shuffle)
+
+
+def _shuffle_arg(shuffle, dictionary) -> int:
+    e = shuffle_code(shuffle)
+    if e != 0 and dictionary is not None:
+        raise ValueError("shuffle and dictionary do not go together: a frame is version 3 or version 4")
+    return e
+
+
+def _no_version_4(info: dict, who: str):
+    if info["version"] == 4:
+        raise ValueError(f"{who}: a version-4 (shuffled) frame is not supported here yet; decode and encode it again")
 
 
 def _flags(store: bool) -> int:
     return FRAME_STORED if store else 0
 
 
-def frame_bound(nbytes: int, block_bits: int = 18, store: bool = False, dictionary: bool = False) -> int:
+def frame_bound(nbytes: int, block_bits: int = 18, store: bool = False, dictionary: bool = False,
+                shuffle: int = 0) -> int:
     """worst-case size of the frame of `nbytes` bytes of content"""
+    if shuffle_code(shuffle) != 0:
+        return int(N.lib().sqz_frame_bound_shuf(nbytes, block_bits, _flags(store) | FRAME_SHUFFLE))
     if dictionary:
         return int(N.lib().sqz_frame_bound_dict(nbytes, block_bits, _flags(store) | FRAME_DICT))
     return int(N.lib().sqz_frame_bound_ex(nbytes, block_bits, _flags(store)))
@@ -45,7 +73,7 @@ class _FrameInfo(dict):
     fields."""
 
     def __missing__(self, key):
-        if key in ("dict_bytes", "dict_crc"):
+        if key in ("dict_bytes", "dict_crc", "elem_bytes"):
             return 0
         raise KeyError(key)
 
@@ -56,6 +84,7 @@ def frame_info(frame) -> dict:
     have no record, info["dict_bytes"] and info["dict_crc"] READ as 0 but are NOT keys of the result: `in`, .get(),
     iteration and the `info` tool show them for a version-3 frame only, so that the result of an older frame keeps
     exactly the header's own eight fields.  Test the version (info["version"] == 3), not the key.
+    elem_bytes: the record of a version-4 frame, in the same way a key for version 4 only (0 while it is not in reach).
     Host code: no device is touched."""
     frame = bytes(frame)
     fi = N.FrameInfo()
@@ -66,6 +95,11 @@ def frame_info(frame) -> dict:
         if len(frame) >= fi.payload_off:
             _raise(N.lib().sqz_frame_dict(frame, len(frame), C.byref(nb), C.byref(crc)), "sqz_frame_dict")
         info["dict_bytes"], info["dict_crc"] = nb.value, crc.value
+    if fi.version == 4:
+        eb = C.c_uint32(0)
+        if len(frame) >= fi.payload_off:
+            _raise(N.lib().sqz_frame_elem(frame, len(frame), C.byref(eb)), "sqz_frame_elem")
+        info["elem_bytes"] = eb.value
     return info
 
 
@@ -80,17 +114,21 @@ def frame_blocks(frame) -> list:
 
 
 def compress_frame(data, win_bits: int = 15, block_bits: int = 18, store: bool = False,
-                   parse: str = "greedy", dictionary=None) -> bytes:
+                   parse: str = "greedy", dictionary=None, shuffle: int = 0) -> bytes:
     lazy = parse_code(parse) == PARSE_LAZY
+    elem = _shuffle_arg(shuffle, dictionary)
     dct = dict_bytes(dictionary, 1 << win_bits) if dictionary is not None else None
     data = bytes(data)
-    cap = frame_bound(len(data), block_bits, store, dct is not None)
+    cap = frame_bound(len(data), block_bits, store, dct is not None, elem)
     if cap == 0:
         raise SqzError(errno.EINVAL, "sqz_frame_compress: block_bits out of range")
     out = bytearray(cap)
     n = C.c_uint64(0)
     dst = (C.c_uint8 * cap).from_buffer(out)
-    if dct is not None:
+    if elem != 0:
+        _raise(N.lib().sqz_frame_compress_shuf(data, len(data), win_bits, block_bits, _flags(store) | FRAME_SHUFFLE,
+                                               parse_code(parse), elem, dst, cap, C.byref(n)), "sqz_frame_compress_shuf")
+    elif dct is not None:
         _raise(N.lib().sqz_frame_compress_dict(data, len(data), win_bits, block_bits, _flags(store), parse_code(parse),
                                                dct, len(dct), dst, cap, C.byref(n)), "sqz_frame_compress_dict")
     elif lazy:
@@ -118,6 +156,8 @@ def decompress_frame(frame, return_errors: bool = False, dictionary=None):
     if dct is not None:
         rc = N.lib().sqz_frame_decompress_dict(frame, len(frame), dct, len(dct), dst, fi["content_bytes"], C.byref(n),
                                                errs)
+    elif fi["version"] == 4:
+        rc = N.lib().sqz_frame_decompress_shuf(frame, len(frame), dst, fi["content_bytes"], C.byref(n), errs)
     else:
         rc = N.lib().sqz_frame_decompress(frame, len(frame), dst, fi["content_bytes"], C.byref(n), errs)
     del dst
@@ -136,11 +176,14 @@ def read_range(frame, offset: int, length: int, dictionary=None) -> bytes:
     dictionary: as for decompress_frame."""
     dct = dict_bytes(dictionary) if dictionary is not None else None
     frame = bytes(frame)
-    content = frame_info(frame[:HEADER_BYTES])["content_bytes"]
+    fi = frame_info(frame[:HEADER_BYTES])
+    content = fi["content_bytes"]
     out = bytearray(max(min(length, content), 1))            # a range that leaves the content is refused below
     dst = (C.c_uint8 * len(out)).from_buffer(out)
     if dct is not None:
         rc = N.lib().sqz_frame_read_dict(frame, len(frame), dct, len(dct), offset, length, dst)
+    elif fi["version"] == 4:
+        rc = N.lib().sqz_frame_read_shuf(frame, len(frame), offset, length, dst)
     else:
         rc = N.lib().sqz_frame_read(frame, len(frame), offset, length, dst)
     del dst
@@ -168,6 +211,38 @@ def crc32_blocks(d_in, in_off, crc=None):
     return crc[:n]
 
 
+def shuffle_blocks(d_in, offsets, elem_bytes: int, inverse: bool = False, d_out=None):
+    """The byte shuffle of version 4 over n ragged ranges of a uint8 tensor: offsets int64[n + 1] on the device, range b
+    = d_in[offsets[b] : offsets[b + 1]], each transposed on its own into the same place of d_out (a tensor of d_in's
+    size, made when not given; it must not overlap d_in): all first bytes of its elem_bytes-wide elements, then all
+    second bytes, ..., the tail bytes behind; inverse=True undoes it.  Bytes outside every range are not written.
+    Enqueues and returns d_out."""
+    import torch
+    if elem_bytes not in (2, 4, 8):
+        raise ValueError(f"elem_bytes must be 2, 4 or 8, not {elem_bytes!r}")
+    if d_in.dtype != torch.uint8 or d_in.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1:
+        raise ValueError("shuffle_blocks: a one-dimensional uint8 tensor and int64 offsets")
+    if d_out is None:
+        d_out = torch.empty_like(d_in)
+    elif d_out.dtype != torch.uint8 or d_out.numel() < d_in.numel():
+        raise ValueError("shuffle_blocks: d_out must be a uint8 tensor of d_in's size")
+    n = max(offsets.numel() - 1, 0)
+    _raise(N.lib().sqz_hip_shuffle_blocks(_ptr(d_in), _ptr(offsets), n, elem_bytes, 1 if inverse else 0, _ptr(d_out),
+                                          _stream()), "sqz_hip_shuffle_blocks")
+    return d_out
+
+
+def _info_dev(d_frame):
+    """frame_info() of a device-resident frame: one 32-byte copy, and for version 4 the record's 8 bytes behind the
+    index, which say what the elements are"""
+    info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    if info["version"] == 4:
+        at = HEADER_BYTES + 8 * info["n_blocks"]
+        if d_frame.numel() >= at + 8:
+            info["elem_bytes"] = int.from_bytes(d_frame[at:at + 4].cpu().numpy().tobytes(), "little")
+    return info
+
+
 def _dict_dev(dictionary, window, device):
     """A shared dictionary on the device, its length checked before anything native is called: bytes-like, or a
     uint8 tensor that is there already (used as it is: the caller keeps it alive until the stream has passed).
@@ -189,25 +264,29 @@ class FrameEncoder:
     """Reusable device buffers for frames of up to `content_bytes` bytes at (win_bits, block_bits).
     encode() enqueues and returns; frame_bytes / status / err are device tensors to read after a synchronise.
     dictionary (bytes-like or a uint8 device tensor of 1 .. window - 1 bytes): version-3 frames, byte for byte
-    compress_frame(..., dictionary=)'s; it is kept on the device for the encoder's life."""
+    compress_frame(..., dictionary=)'s; it is kept on the device for the encoder's life.
+    shuffle (2, 4 or 8; not with a dictionary): version-4 frames, byte for byte compress_frame(..., shuffle=)'s."""
 
     def __init__(self, content_bytes: int, win_bits: int = 15, block_bits: int = 18, capacity: int = None,
-                 device="cuda", store: bool = False, parse: str = "greedy", dictionary=None):
+                 device="cuda", store: bool = False, parse: str = "greedy", dictionary=None, shuffle: int = 0):
         import torch
         self.parse = parse_code(parse)
+        self.elem = _shuffle_arg(shuffle, dictionary)
         L = N.lib()
         self.win_bits, self.block_bits, self.content_bytes = win_bits, block_bits, content_bytes
         self.flags = _flags(store)
         self.dictionary = _dict_dev(dictionary, 1 << win_bits, device) if dictionary is not None else None
         if capacity is None:
-            capacity = frame_bound(content_bytes, block_bits, store, self.dictionary is not None)
+            capacity = frame_bound(content_bytes, block_bits, store, self.dictionary is not None, self.elem)
         self.capacity = capacity
         self.n_blocks = (content_bytes + (1 << block_bits) - 1) >> block_bits
         self.frame = torch.empty(max(self.capacity, 16), dtype=torch.uint8, device=device)
         self.frame_bytes = torch.zeros(1, dtype=torch.int64, device=device)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
         self.err = torch.zeros(max(self.n_blocks, 1), dtype=torch.int32, device=device)
-        if self.dictionary is not None:
+        if self.elem != 0:
+            self.scratch_bytes = int(L.sqz_hip_frame_scratch_bytes_shuf(content_bytes, block_bits, 1, self.flags))
+        elif self.dictionary is not None:
             self.scratch_bytes = int(L.sqz_hip_frame_scratch_bytes_dict(content_bytes, block_bits, 1, self.flags,
                                                                         self.dictionary.numel()))
         else:
@@ -218,6 +297,12 @@ class FrameEncoder:
         nbytes = d_in.numel() if content_bytes is None else content_bytes
         if nbytes > self.content_bytes:
             raise SqzError(errno.E2BIG, "FrameEncoder: more content than the buffers were made for")
+        if self.elem != 0:
+            _raise(N.lib().sqz_hip_frame_encode_shuf(
+                _ptr(d_in), nbytes, self.win_bits, self.block_bits, self.flags | FRAME_SHUFFLE, self.parse, self.elem,
+                _ptr(self.frame), self.capacity, _ptr(self.frame_bytes), _ptr(self.status), _ptr(self.err),
+                _ptr(self.scratch), self.scratch_bytes, _stream()), "sqz_hip_frame_encode_shuf")
+            return self.frame, self.frame_bytes, self.status, self.err
         if self.dictionary is not None:
             _raise(N.lib().sqz_hip_frame_encode_dict(
                 _ptr(d_in), nbytes, self.win_bits, self.block_bits, self.flags | FRAME_DICT, self.parse,
@@ -263,11 +348,12 @@ def decode_frame(d_frame, d_out, info: dict = None, err=None, status=None, scrat
     with one 32-byte copy when not given).  Enqueues and returns (err int32[n_blocks], status int32[1]).
     dictionary (bytes-like or a uint8 device tensor): what a version-3 frame was written with; a wrong one is status
     EILSEQ with nothing written, a frame of version 1 or 2 with one EINVAL.  Without one the call knows versions 1
-    and 2 and refuses a version-3 frame (status EINVAL)."""
+    and 2 and refuses a version-3 frame (status EINVAL).  A version-4 frame is decoded by what `info` says about its
+    elements (info["elem_bytes"]; a second small copy fetches the record when `info` is not given)."""
     import torch
     L = N.lib()
     if info is None:
-        info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+        info = _info_dev(d_frame)
     n, content = info["n_blocks"], info["content_bytes"]
     if d_out.numel() < content:
         raise SqzError(errno.E2BIG, "decode_frame: d_out is smaller than the content")
@@ -284,6 +370,14 @@ def decode_frame(d_frame, d_out, info: dict = None, err=None, status=None, scrat
                                            _ptr(err), _ptr(status), _ptr(scratch), scratch.numel(), _stream()),
                "sqz_hip_frame_decode_dict")
         return err[:n], status
+    if info["version"] == 4 and dictionary is None:
+        bits = info["block_bytes"].bit_length() - 1
+        if scratch is None:
+            scratch = _scratch_for(d_out.device, int(L.sqz_hip_frame_scratch_bytes_shuf(content, bits, 0, FRAME_SHUFFLE)))
+        _raise(L.sqz_hip_frame_decode_shuf(_ptr(d_frame), d_frame.numel(), n, content, info["elem_bytes"], _ptr(d_out),
+                                           _ptr(err), _ptr(status), _ptr(scratch), scratch.numel(), _stream()),
+               "sqz_hip_frame_decode_shuf")
+        return err[:n], status
     need = int(L.sqz_hip_frame_scratch_bytes(content, info["block_bytes"].bit_length() - 1, 0))
     if scratch is None:
         scratch = _scratch_for(d_out.device, need)
@@ -298,11 +392,11 @@ def read_frame(d_frame, offset: int, length: int, d_out=None, info: dict = None,
     the covering blocks are decoded, into the scratch, and verified.  `info` as for decode_frame; dictionary: as
     for decode_frame, needed for a version-3 frame.  Enqueues and returns (d_out[:length], err int32[covering
     blocks], status int32[1]): d_out holds the range when status is 0 after a synchronise and is untouched
-    otherwise.  A range that leaves the content raises EINVAL here."""
+    otherwise.  A range that leaves the content raises EINVAL here.  Version 4: as for decode_frame."""
     import torch
     L = N.lib()
     if info is None:
-        info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+        info = _info_dev(d_frame)
     n, content, bits = info["n_blocks"], info["content_bytes"], info["block_bytes"].bit_length() - 1
     device = d_frame.device
     d = _dict_dev(dictionary, 1 << info["win_bits"], device) if dictionary is not None else None
@@ -315,6 +409,13 @@ def read_frame(d_frame, offset: int, length: int, d_out=None, info: dict = None,
         err = torch.zeros(max(covering, 1), dtype=torch.int32, device=device)
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=device)
+    if info["version"] == 4 and d is None:
+        if scratch is None:
+            scratch = _scratch_for(device, int(L.sqz_hip_frame_read_scratch_bytes_shuf(length, bits)))
+        _raise(L.sqz_hip_frame_read_shuf(_ptr(d_frame), d_frame.numel(), n, content, bits, info["elem_bytes"], offset,
+                                         length, _ptr(d_out), _ptr(err), _ptr(status), _ptr(scratch), scratch.numel(),
+                                         _stream()), "sqz_hip_frame_read_shuf")
+        return d_out[:length], err[:covering], status
     if scratch is None:
         scratch = _scratch_for(device, int(L.sqz_hip_frame_read_scratch_bytes(length, bits)))
     if d is not None:
@@ -366,6 +467,7 @@ def gather_frame(d_frame, offsets, lengths, max_length: int = None, max_blocks: 
     L = N.lib()
     if info is None:
         info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    _no_version_4(info, "gather_frame")
     n, content, bits = info["n_blocks"], info["content_bytes"], info["block_bytes"].bit_length() - 1
     device = d_frame.device
     d = _dict_dev(dictionary, 1 << info["win_bits"], device) if dictionary is not None else None
@@ -424,6 +526,7 @@ def update_frame(d_frame, offsets, lengths, data, max_length: int = None, max_bl
     parse = parse_code(parse)
     if info is None:
         info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    _no_version_4(info, "update_frame")
     n, content, bits = info["n_blocks"], info["content_bytes"], info["block_bytes"].bit_length() - 1
     device = d_frame.device
     d = _dict_dev(dictionary, 1 << info["win_bits"], device) if dictionary is not None else None
@@ -502,6 +605,7 @@ def append_frame(d_frame, data, d_out=None, info: dict = None, dictionary=None, 
     parse = parse_code(parse)
     if info is None:
         info = frame_info(d_frame[:HEADER_BYTES].cpu().numpy().tobytes())
+    _no_version_4(info, "append_frame")
     n, content, bits = info["n_blocks"], info["content_bytes"], info["block_bytes"].bit_length() - 1
     device = d_frame.device
     d = _dict_dev(dictionary, 1 << info["win_bits"], device) if dictionary is not None else None
@@ -537,6 +641,7 @@ def append_frame(d_frame, data, d_out=None, info: dict = None, dictionary=None, 
 
 def _append_file(frame: bytes, data: bytes, dictionary, parse: str) -> bytes:
     """the file tool's `a`: FRAME and IN through append_frame, the new frame as bytes (SqzError on a status)"""
+    _no_version_4(frame_info(frame[:HEADER_BYTES]), "append")       # before anything native, torch included, runs
     import torch
     d_frame = torch.frombuffer(bytearray(frame) + bytearray(16), dtype=torch.uint8)[:len(frame)].to("cuda")
     d_out, frame_bytes, _, status = append_frame(d_frame, data, info=frame_info(frame), dictionary=dictionary,
@@ -560,6 +665,8 @@ def main(argv=None) -> int:
     c.add_argument("--lazy", action="store_true", help="lazy parse: smaller streams, same format (not the reference's bytes)")
     c.add_argument("--dict", dest="dictionary", metavar="FILE",
                    help="version 3: every block may reach back into FILE's bytes (1 .. window - 1 of them)")
+    c.add_argument("--shuffle", type=int, default=0, metavar="N",
+                   help="version 4: byte-shuffle every block as elements of N = 2, 4 or 8 bytes (not with --dict)")
     d = sub.add_parser("d", help="decompress IN to OUT")
     d.add_argument("src")
     d.add_argument("dst")
@@ -584,7 +691,9 @@ def main(argv=None) -> int:
     try:
         if a.cmd == "c":
             parse = "lazy" if a.lazy else "greedy"
-            if dct is None:
+            if a.shuffle != 0:
+                out = compress_frame(blob, a.win_bits, a.block_bits, a.store, parse, dictionary=dct, shuffle=a.shuffle)
+            elif dct is None:
                 out = compress_frame(blob, a.win_bits, a.block_bits, a.store, parse)
             else:
                 out = compress_frame(blob, a.win_bits, a.block_bits, a.store, parse, dictionary=dct)
