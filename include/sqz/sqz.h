@@ -927,6 +927,71 @@ SQZ_API int sqz_hip_frame_append_dict(const void* d_frame, uint64_t avail, uint3
                                       uint64_t capacity, uint64_t* d_frame_bytes, uint32_t* d_blocks_encoded,
                                       int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
 
+/* MANY frames in one call, for a caller whose unit is the frame itself: one file per sample, per tensor, per shard.  A
+ * frame call costs about one block's dependent chain whether it holds one block or thousands; k frames in one call run
+ * their blocks through ONE launch chain, and the number of launches does not depend on k.  Device pointers; d_frames,
+ * d_scratch 16-byte aligned; asynchronous, no host synchronisation inside.  Versions 1 and 2 only.  There is no format
+ * change: every frame a batch writes is byte for byte the frame sqz_hip_frame_encode_parse writes for the same content
+ * and arguments, and what a batch decodes is what sqz_hip_frame_decode delivers.  A frame that is refused or fails costs
+ * that frame alone: its neighbours are written or delivered as if it were not there.
+ *
+ * ENCODE.  content_bytes: a HOST array of k sizes, brought to the device by one asynchronous copy on `stream` in front
+ * of the first kernel (the array must stay as it is until that copy has run); the contents lie back to back in d_in.
+ * One win_bits, block_bits, flags (0 or SQZ_FRAME_STORED) and parse for the call.  Frame f is written at d_frames +
+ * frame_at[f], frame_at[f] = the sum over g < f of sqz_frame_bound_ex(content_bytes[g], block_bits, flags) rounded up
+ * to 16; sqz_hip_frames_bound returns frame_at[k] (and the k + 1 offsets when frame_at is not NULL), 0 for parameters
+ * out of range or sizes that wrap.  d_frame_bytes[f] and d_status[f] (k entries each) are the single call's: the status
+ * is 0 or the first failed block's errno, and then nothing of that frame is written.  d_err has one entry per block of
+ * the whole batch, frame f's from sum(n_blocks[g], g < f) on.  Bytes between the end of a frame and frame_at[f + 1] are
+ * not touched.  An empty content gives the 32-byte frame.
+ * EINVAL at the call, nothing enqueued: flags with another bit, a parse that is none, win_bits outside 10..15 or
+ *   block_bits outside 12..24; a null content_bytes, d_frames, d_frame_bytes, d_status or d_scratch, a null d_in or
+ *   d_err where there is content; d_frames or d_scratch misaligned; capacity below sqz_hip_frames_bound (so no frame
+ *   can fail to fit); total blocks + k above 2^31 - 1; a scratch smaller than the function says.  k == 0 returns 0 and
+ *   enqueues nothing.  ENODEV without a device (after the argument checks).
+ * Scratch, with T = total blocks, S = total content, b = block_bits, every term rounded up to 256:
+ *       sqz_hip_frames_encode_scratch_bytes = 8 k + 2 * 8 (k + 1) + 4 (k + 1)     [sizes; in_at, frame_at; first blocks]
+ *           + 2 * 8 (T + 1) + (4 T + 4) + 2 * 8 T                   [the encoder's two offset lists, the checksums,
+ *                                                                     stream sizes and copy sizes]
+ *           + 8 (T + k) + 8 (T + 1) + (STORED ? 4 T + 4 : 0)        [dense offsets per frame and absolute, stored mask]
+ *           + T * sqz_bound(2^b) + sqz_hip_encode_scratch_bytes(T, S); 0 for parameters out of range.
+ *
+ * DECODE.  items: a HOST array of k entries, what sqz_frame_info said about a host copy of each header (n_blocks,
+ * content_bytes), where the frame lies in d_frames (frame_at, a multiple of 16; avail bytes of it are there) and where
+ * its content goes in d_out (out_at); `zero` must be 0.  Any mix of versions 1 and 2, each frame with its own win_bits
+ * and block_bits.  The table is brought to the device like the sizes of an encode.  d_status has k entries, d_err one per
+ * block of the batch as above.  Per frame the checks are sqz_hip_frame_decode's in its order; a refused frame has its
+ * status in d_status[f] and in every one of its d_err entries, none of its payload is read and none of its output is
+ * written.  A frame of version 3 or 4 is refused in this way (EINVAL).  For an accepted frame d_err is what
+ * sqz_hip_frame_decode leaves, EILSEQ for a block whose checksum does not hold included; its other blocks are delivered.
+ * EINVAL at the call, nothing enqueued: a frame_at that is no multiple of 16; zero != 0; frames or outputs that are
+ *   not ascending and disjoint (frame_at[f] + avail[f] <= frame_at[f + 1], out_at[f] + content_bytes[f] <=
+ *   out_at[f + 1], neither sum wrapping); total blocks + k above 2^31 - 1; a null items, d_frames, d_status or
+ *   d_scratch, a null d_out or d_err where there are blocks; d_frames or d_scratch misaligned; a scratch smaller than
+ *   the function says.  E2BIG when an avail is below 32 + 8 n_blocks.  k == 0 returns 0 and enqueues nothing.  ENODEV
+ *   without a device (after the argument checks).
+ * Scratch, with T = total blocks, E = T + k entries (every frame has one more than blocks: a switched-off entry that
+ * reaches over the next frame's header and index), X = out_at[k - 1] + content_bytes[k - 1] - out_at[0] (the decoder
+ * keeps one word per byte of that span: gaps between outputs cost scratch), every term rounded up to 256:
+ *       sqz_hip_frames_decode_scratch_bytes = 40 k + 4 (k + 1) + 2 * 8 (E + 1) + 4 * (4 E + 4)
+ *           + sqz_hip_decode_scratch_bytes(E, X); 0 for a table the call would refuse.                              */
+struct sqz_frames_item {
+    uint64_t frame_at, avail, content_bytes, out_at;
+    uint32_t n_blocks, zero;
+};
+SQZ_API uint64_t sqz_hip_frames_bound(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits, uint32_t flags,
+                                      uint64_t* frame_at /* k + 1 entries, may be NULL */);
+SQZ_API uint64_t sqz_hip_frames_encode_scratch_bytes(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits,
+                                                     uint32_t flags);
+SQZ_API int sqz_hip_frames_encode(const void* d_in, const uint64_t* content_bytes, uint32_t k, uint32_t win_bits,
+                                  uint32_t block_bits, uint32_t flags, uint32_t parse, void* d_frames, uint64_t capacity,
+                                  uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err, void* d_scratch,
+                                  uint64_t scratch_bytes, void* stream);
+SQZ_API uint64_t sqz_hip_frames_decode_scratch_bytes(const struct sqz_frames_item* items, uint32_t k);
+SQZ_API int sqz_hip_frames_decode(const void* d_frames, const struct sqz_frames_item* items, uint32_t k, void* d_out,
+                                  int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                  void* stream);
+
 /* Live timing of the last kernels enqueued through this library on the
  * calling thread's context, measured with HIP events ON THE LAUNCH STREAM.
  * Enabled with sqz_hip_set_timing(1); values in milliseconds.               */

@@ -10,10 +10,12 @@ from .codec import (SqzError, bound, compress, decompress, device_info,  # noqa:
 
 __all__ = ["SqzError", "bound", "compress", "decompress", "device_info", "file_words",
            "MIN_WIN_BITS", "MAX_WIN_BITS", "compress_frame", "decompress_frame", "frame_info", "read_range",
-           "frame_blocks", "frame_bound", "gather_frame", "update_frame", "append_frame", "shuffle_blocks"]
+           "frame_blocks", "frame_bound", "gather_frame", "update_frame", "append_frame", "shuffle_blocks",
+           "frames_bound", "encode_frames", "decode_frames", "compress_frames", "decompress_frames"]
 
 _FRAME = ("compress_frame", "decompress_frame", "frame_info", "read_range", "frame_blocks", "frame_bound", "gather_frame", "update_frame",
-          "append_frame", "shuffle_blocks")
+          "append_frame", "shuffle_blocks", "frames_bound", "encode_frames", "decode_frames", "compress_frames",
+          "decompress_frames")
 
 
 def __getattr__(name):

@@ -68,6 +68,12 @@ class FrameBlock(C.Structure):
                [(n, C.c_uint32) for n in ("content_crc", "stored")]
 
 
+class FramesItem(C.Structure):
+    """struct sqz_frames_item of include/sqz/sqz.h: one frame of a batched decode."""
+    _fields_ = [(n, C.c_uint64) for n in ("frame_at", "avail", "content_bytes", "out_at")] + \
+               [(n, C.c_uint32) for n in ("n_blocks", "zero")]
+
+
 class Timing(C.Structure):
     """sqz_hip_timing: per-kernel summed durations (HIP events on the launch stream)."""
     _fields_ = [("ms", C.c_float * 12), ("launches", C.c_uint32 * 12)]
@@ -213,6 +219,12 @@ PROTOTYPES = {
     "sqz_hip_frame_append_dict": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp,
                                             C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, _vp,
                                             C.c_uint64, _vp]),
+    "sqz_hip_frames_bound": (C.c_uint64, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "sqz_hip_frames_encode_scratch_bytes": (C.c_uint64, [_vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "sqz_hip_frames_encode": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                        C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_frames_decode_scratch_bytes": (C.c_uint64, [_vp, C.c_uint32]),
+    "sqz_hip_frames_decode": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
     "sqz_hip_set_finder": (None, [C.c_int]),
     "sqz_hip_get_finder": (C.c_int, []),
     "sqz_hip_set_timing": (None, [C.c_int]),

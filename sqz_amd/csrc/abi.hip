@@ -2785,6 +2785,224 @@ int sqz_hip_frame_append_dict(const void* d_frame, uint64_t avail, uint32_t n_bl
                              d_scratch, scratch_bytes, stream);
 }
 
+// ---- many frames in one call ("Batches of frames")
+// what the host works out from the k sizes of an encode: total blocks, total content, frame_at[k]; !ok: a size wraps,
+// or blocks + k does not fit 31 bits
+struct FramesEncShape { uint64_t blocks, content, bound; bool ok; };
+static FramesEncShape frames_enc_shape(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits, uint32_t flags,
+                                       uint64_t* frame_at) {
+    FramesEncShape S = {0, 0, 0, false};
+    for (uint32_t f = 0; f < k; f++) {
+        const uint64_t c = content_bytes[f];
+        if (c > (1ull << 62)) { return S; }                     // twice the content and more: the bound would wrap
+        const uint64_t slot = align_up(sqz_frame_bound_ex(c, block_bits, flags), 16);
+        if (frame_at != NULL) { frame_at[f] = S.bound; }
+        if (slot == 0 || S.bound > ~slot || S.content > ~c) { return S; }
+        S.bound += slot;
+        S.content += c;
+        S.blocks += frame_blocks(c, block_bits);
+        if (S.blocks + k > 0x7FFFFFFFull) { return S; }
+    }
+    if (frame_at != NULL) { frame_at[k] = S.bound; }
+    S.ok = true;
+    return S;
+}
+
+struct FramesEncScratch {
+    uint64_t content, in_at, frame_at, base, in_off, slab_off, crc, out_bytes, copy_bytes, dense_rel, dense_off, stored,
+             slabs, codec, codec_bytes, total;
+};
+static FramesEncScratch frames_enc_scratch(uint64_t k, uint64_t n, uint64_t content_bytes, uint64_t slab_bytes, bool store) {
+    FramesEncScratch L = {};
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) { const uint64_t r = at; at += align_up(bytes, 256); return r; };
+    L.content = take(k * 8);
+    L.in_at = take((k + 1) * 8);
+    L.frame_at = take((k + 1) * 8);
+    L.base = take((k + 1) * 4);
+    L.in_off = take((n + 1) * 8);
+    L.slab_off = take((n + 1) * 8);
+    L.crc = take(n * 4 + 4);
+    L.out_bytes = take(n * 8);
+    L.copy_bytes = take(n * 8);
+    L.dense_rel = take((n + k) * 8);
+    L.dense_off = take((n + 1) * 8);
+    L.stored = store ? take(n * 4 + 4) : 0;
+    L.slabs = take(n * slab_bytes);
+    L.codec_bytes = sqz_hip_encode_scratch_bytes((uint32_t)n, content_bytes);
+    L.codec = take(L.codec_bytes);
+    L.total = at;
+    return L;
+}
+
+uint64_t sqz_hip_frames_bound(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits, uint32_t flags,
+                              uint64_t* frame_at) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        !frame_flags_ok(flags) || (content_bytes == NULL && k > 0)) { return 0; }
+    const FramesEncShape S = frames_enc_shape(content_bytes, k, block_bits, flags, frame_at);
+    return S.ok ? S.bound : 0;
+}
+
+uint64_t sqz_hip_frames_encode_scratch_bytes(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits,
+                                             uint32_t flags) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        !frame_flags_ok(flags) || (content_bytes == NULL && k > 0)) { return 0; }
+    const FramesEncShape S = frames_enc_shape(content_bytes, k, block_bits, flags, NULL);
+    if (!S.ok) { return 0; }
+    return frames_enc_scratch(k, S.blocks, S.content, sqz_bound(1ull << block_bits), (flags & SQZ_FRAME_STORED) != 0).total;
+}
+
+int sqz_hip_frames_encode(const void* d_in, const uint64_t* content_bytes, uint32_t k, uint32_t win_bits,
+                          uint32_t block_bits, uint32_t flags, uint32_t parse, void* d_frames, uint64_t capacity,
+                          uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err, void* d_scratch,
+                          uint64_t scratch_bytes, void* stream) {
+    if (!parse_ok(parse) || !frame_flags_ok(flags) || !frame_params_ok(win_bits, block_bits)) { return EINVAL; }
+    if (k == 0) { return 0; }
+    if (content_bytes == NULL || d_frames == NULL || ((uintptr_t)d_frames & 15u) != 0 || d_frame_bytes == NULL ||
+        d_status == NULL || d_scratch == NULL || ((uintptr_t)d_scratch & 15u) != 0) { return EINVAL; }
+    const FramesEncShape S = frames_enc_shape(content_bytes, k, block_bits, flags, NULL);
+    if (!S.ok || (d_in == NULL && S.content > 0) || (d_err == NULL && S.blocks > 0) || capacity < S.bound) { return EINVAL; }
+    const uint64_t bb = 1ull << block_bits, slab = sqz_bound(bb);
+    const bool store = (flags & SQZ_FRAME_STORED) != 0;
+    const uint32_t n = (uint32_t)S.blocks;
+    const FramesEncScratch L = frames_enc_scratch(k, n, S.content, slab, store);
+    if (scratch_bytes < L.total) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* const scratch = (uint8_t*)d_scratch;
+    uint64_t* sizes = (uint64_t*)(scratch + L.content);
+    uint64_t* in_at = (uint64_t*)(scratch + L.in_at);
+    uint64_t* frame_at = (uint64_t*)(scratch + L.frame_at);
+    uint32_t* base = (uint32_t*)(scratch + L.base);
+    uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
+    uint64_t* slab_off = (uint64_t*)(scratch + L.slab_off);
+    uint32_t* crc = (uint32_t*)(scratch + L.crc);
+    uint64_t* out_bytes = (uint64_t*)(scratch + L.out_bytes);
+    uint64_t* copy_bytes = (uint64_t*)(scratch + L.copy_bytes);
+    uint64_t* dense_rel = (uint64_t*)(scratch + L.dense_rel);
+    uint64_t* dense_off = (uint64_t*)(scratch + L.dense_off);
+    uint32_t* stored = store ? (uint32_t*)(scratch + L.stored) : nullptr;
+    HIP_TRY(hipMemcpyAsync(sizes, content_bytes, (size_t)k * 8, hipMemcpyHostToDevice, st));
+    sqzk::launch_frames_encode_scan(sizes, k, block_bits, flags, in_at, frame_at, base, st);
+    sqzk::launch_frames_plan(sizes, in_at, base, k, block_bits, slab, in_off, slab_off, st);
+    if (n > 0) {
+        { SpanGuard g(st, SQZ_HIP_K_CRC32);
+          sqzk::launch_crc32_blocks((const uint8_t*)d_in, in_off, n, crc, bb, st); }
+        const uint64_t head = align_up((uint64_t)n * 4, 256);
+        const uint64_t slots = (L.codec_bytes - head) / 8;
+        uint32_t* counts = (uint32_t*)(scratch + L.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + L.codec + head);
+        run_encode(finder_for(parse), (const uint8_t*)d_in, in_off, n, 1u << win_bits, tokens, counts, tokens,
+                   tokens + slots, bb, scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st, parse);
+    }
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frames_index(out_bytes, d_err, crc, sizes, frame_at, base, k, win_bits, block_bits, flags,
+                                (uint8_t*)d_frames, copy_bytes, dense_rel, dense_off, stored, d_frame_bytes, d_status, st); }
+    if (n > 0) {
+        sqzk::launch_compact_blocks(scratch + L.slabs, slab_off, copy_bytes, n, (uint8_t*)d_frames, dense_off, bb / 2, st);
+        if (store) {                                        // the stored blocks' content, where the indexes say
+            SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
+            sqzk::launch_range_copy((const uint8_t*)d_in, in_off, (uint8_t*)d_frames, dense_off, in_off, stored, n, true,
+                                    bb, st);
+        }
+    }
+    return hip_errno(hipGetLastError());
+}
+
+// what the host works out from the table of a decode: total blocks, the span of the outputs, the largest block's size
+// as far as the table says (it only sizes launches); err: EINVAL / E2BIG as the call answers them
+struct FramesDecShape { uint64_t blocks, extent, hint; int err; };
+static FramesDecShape frames_dec_shape(const struct sqz_frames_item* items, uint32_t k) {
+    FramesDecShape S = {0, 0, 1, 0};
+    for (uint32_t f = 0; f < k; f++) {
+        const struct sqz_frames_item& it = items[f];
+        if ((it.frame_at & 15u) != 0 || it.zero != 0 || it.avail > ~it.frame_at || it.content_bytes > ~it.out_at) {
+            S.err = EINVAL;
+            return S;
+        }
+        if (f + 1 < k && (it.frame_at + it.avail > items[f + 1].frame_at ||
+                          it.out_at + it.content_bytes > items[f + 1].out_at)) { S.err = EINVAL; return S; }
+        S.blocks += it.n_blocks;
+        if (S.blocks + k > 0x7FFFFFFFull) { S.err = EINVAL; return S; }
+        if (it.n_blocks > 0) {
+            const uint64_t per = (it.content_bytes + it.n_blocks - 1) / it.n_blocks;
+            if (per > S.hint) { S.hint = per; }
+        }
+    }
+    if (k > 0) { S.extent = items[k - 1].out_at + items[k - 1].content_bytes - items[0].out_at; }
+    if (S.extent > (1ull << 60)) { S.err = EINVAL; return S; }     // four bytes of scratch per byte of it
+    for (uint32_t f = 0; f < k; f++) {
+        if (items[f].avail < 32 + 8 * (uint64_t)items[f].n_blocks) { S.err = E2BIG; return S; }
+    }
+    return S;
+}
+
+struct FramesDecScratch { uint64_t items, base, in_off, out_off, skip, stored, crc, err, codec, codec_bytes, total; };
+static FramesDecScratch frames_dec_scratch(uint64_t k, uint64_t entries, uint64_t extent) {
+    FramesDecScratch L = {};
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) { const uint64_t r = at; at += align_up(bytes, 256); return r; };
+    L.items = take(k * sizeof(struct sqz_frames_item));
+    L.base = take((k + 1) * 4);
+    L.in_off = take((entries + 1) * 8);
+    L.out_off = take((entries + 1) * 8);
+    L.skip = take(entries * 4 + 4);
+    L.stored = take(entries * 4 + 4);
+    L.crc = take(entries * 4 + 4);
+    L.err = take(entries * 4 + 4);
+    L.codec_bytes = sqz_hip_decode_scratch_bytes((uint32_t)entries, extent);
+    L.codec = take(L.codec_bytes);
+    L.total = at;
+    return L;
+}
+static_assert(sizeof(struct sqz_frames_item) == 40, "the table of a batched decode: 40 bytes per frame (sqz.h)");
+
+uint64_t sqz_hip_frames_decode_scratch_bytes(const struct sqz_frames_item* items, uint32_t k) {
+    if (items == NULL && k > 0) { return 0; }
+    const FramesDecShape S = frames_dec_shape(items, k);
+    return S.err != 0 ? 0 : frames_dec_scratch(k, S.blocks + k, S.extent).total;
+}
+
+int sqz_hip_frames_decode(const void* d_frames, const struct sqz_frames_item* items, uint32_t k, void* d_out,
+                          int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (k == 0) { return 0; }
+    if (items == NULL || d_frames == NULL || ((uintptr_t)d_frames & 15u) != 0 || d_status == NULL || d_scratch == NULL ||
+        ((uintptr_t)d_scratch & 15u) != 0) { return EINVAL; }
+    const FramesDecShape S = frames_dec_shape(items, k);
+    if (S.err == EINVAL || (S.blocks > 0 && (d_out == NULL || d_err == NULL))) { return EINVAL; }
+    const uint32_t n = (uint32_t)S.blocks, entries = n + k;
+    const FramesDecScratch L = frames_dec_scratch(k, entries, S.extent);
+    if (scratch_bytes < L.total) { return EINVAL; }
+    if (S.err != 0) { return S.err; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* const scratch = (uint8_t*)d_scratch;
+    struct sqz_frames_item* table = (struct sqz_frames_item*)(scratch + L.items);
+    uint32_t* base = (uint32_t*)(scratch + L.base);
+    uint64_t* in_off = (uint64_t*)(scratch + L.in_off);
+    uint64_t* out_off = (uint64_t*)(scratch + L.out_off);
+    uint32_t* skip = (uint32_t*)(scratch + L.skip);
+    uint32_t* stored = (uint32_t*)(scratch + L.stored);
+    uint32_t* crc = (uint32_t*)(scratch + L.crc);
+    int32_t* err = (int32_t*)(scratch + L.err);
+    const uint64_t out_base = items[0].out_at;
+    HIP_TRY(hipMemcpyAsync(table, items, (size_t)k * sizeof(struct sqz_frames_item), hipMemcpyHostToDevice, st));
+    sqzk::launch_frames_decode_scan(table, k, base, st);
+    { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
+      sqzk::launch_frames_open((const uint8_t*)d_frames, table, base, k, out_base, in_off, out_off, skip, stored,
+                               d_status, st); }
+    if (n > 0) {
+        uint32_t* counts = (uint32_t*)(scratch + L.codec);
+        uint32_t* tokens = (uint32_t*)(scratch + L.codec + align_up((uint64_t)entries * 4, 256));
+        run_frame_decode((const uint8_t*)d_frames, in_off, out_off, entries, S.hint, tokens, counts,
+                         (uint8_t*)d_out + out_base, err, skip, stored, crc, DictDev(), st, n);
+        sqzk::launch_frames_verify((const uint8_t*)d_frames, table, base, k, crc, d_status, err, d_err, st);
+    }
+    return hip_errno(hipGetLastError());
+}
+
 int sqz_hip_crc32_blocks(const void* d_in, const uint64_t* d_in_off, uint32_t n, uint32_t* d_crc, void* stream) {
     if (n == 0) { return 0; }
     if (d_in == NULL || d_in_off == NULL || d_crc == NULL) { return EINVAL; }

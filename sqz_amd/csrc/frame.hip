@@ -1878,4 +1878,292 @@ void launch_frame_append_index(const uint8_t* old, uint32_t n_blocks, uint64_t c
     }
 }
 
+// ---------------------------------------------------------------------------------------- batches of frames
+// k frames in one call ("Batches of frames"): one workgroup per frame does what the one
+// workgroup of a single call does, around the same frame_index_body / frame_open_body, so that the number of
+// launches does not depend on k.  The frame's workgroup sums its own index as well -- every lane the entries of its
+// share, joined in LDS -- so there is neither a checksum launch per frame nor one that reads the payload between two
+// indexes, and the seal needs no launch of its own.
+namespace {
+
+constexpr int kFramesThreads = 256;
+
+// x^(64 n): the n index entries (8 bytes each) one lane has summed
+__device__ __forceinline__ uint32_t xpow64_lane(uint64_t n) {
+    uint32_t p = kCrcOne;
+    for (int j = 0; n != 0; j++, n >>= 1) {
+        if ((n & 1u) != 0) { p = gf_mul(p, kCrcTab.pow2[(j + 6) & 31]); }
+    }
+    return p;
+}
+
+// The whole workgroup: lane t brings r = the register after its `count` entries from state 0 (no initial value, no
+// final xor) -- the lanes' shares lie in ascending order -- and every lane gets zlib's crc32 of all entries; *power
+// = x^(8 * their bytes).  (r, p) pairs join by (rA, pA) . (rB, pB) = (rA pB ^ rB, pA pB), in a tree over LDS.
+__device__ __forceinline__ uint32_t index_crc_workgroup(uint32_t r, uint64_t count, uint32_t* power) {
+    __shared__ uint32_t join_r[kFramesThreads];
+    __shared__ uint32_t join_p[kFramesThreads];
+    const uint32_t t = threadIdx.x;
+    join_r[t] = r;
+    join_p[t] = xpow64_lane(count);
+    for (uint32_t s = 1; s < kFramesThreads; s <<= 1) {
+        __syncthreads();
+        if ((t & (2 * s - 1)) == 0) {
+            const uint32_t pb = join_p[t + s];
+            join_r[t] = gf_mul(join_r[t], pb) ^ join_r[t + s];
+            join_p[t] = gf_mul(join_p[t], pb);
+        }
+    }
+    __syncthreads();
+    const uint32_t p = join_p[0];
+    const uint32_t c = join_r[0] ^ gf_mul(0xFFFFFFFFu, p) ^ 0xFFFFFFFFu;
+    __syncthreads();                               // the arrays may be written again
+    *power = p;
+    return c;
+}
+
+// sqz_frame_bound_ex, rounded up to 16: what frame f of a batch may take of d_frames
+__device__ __forceinline__ uint64_t frames_slot_bytes(uint64_t content_bytes, uint32_t block_bits, bool store) {
+    const uint64_t bb = 1ull << block_bits, full = content_bytes >> block_bits, tail = content_bytes & (bb - 1);
+    const uint64_t n = full + (tail != 0 ? 1 : 0);
+    const uint64_t payload_off = (32 + 8 * n + 15) & ~(uint64_t)15;
+    const uint64_t payload = store ? (content_bytes + 7) & ~(uint64_t)7
+                                   : full * ((2 * bb + 1024 + 7) & ~(uint64_t)7) +
+                                     (tail != 0 ? (2 * tail + 1024 + 7) & ~(uint64_t)7 : 0);
+    return (payload_off + payload + 15) & ~(uint64_t)15;
+}
+
+// exclusive scans over the k frames of a batch by one workgroup: lane t sums its share, lane 0 the 256 shares
+template <int kN>
+__device__ __forceinline__ void frames_scan_shares(uint64_t (&mine)[kN], uint64_t (*shares)[kFramesThreads]) {
+    const uint32_t t = threadIdx.x;
+    for (int j = 0; j < kN; j++) { shares[j][t] = mine[j]; }
+    __syncthreads();
+    if (t == 0) {
+        for (int j = 0; j < kN; j++) {
+            uint64_t run = 0;
+            for (int q = 0; q < kFramesThreads; q++) { const uint64_t v = shares[j][q]; shares[j][q] = run; run += v; }
+        }
+    }
+    __syncthreads();
+    for (int j = 0; j < kN; j++) { mine[j] = shares[j][t]; }
+}
+
+} // namespace
+
+// encode, one workgroup: in_at (where frame f's content starts in d_in), frame_at (where its frame starts in
+// d_frames: the bounds, each rounded up to 16) and base (its first block in the batch's arrays), k + 1 entries each
+__global__ __launch_bounds__(kFramesThreads)
+void frames_encode_scan_kernel(const uint64_t* __restrict__ content_bytes, uint32_t k, uint32_t block_bits,
+                               uint32_t flags, uint64_t* __restrict__ in_at, uint64_t* __restrict__ frame_at,
+                               uint32_t* __restrict__ base) {
+    __shared__ uint64_t shares[3][kFramesThreads];
+    const uint32_t t = threadIdx.x;
+    const bool store = (flags & kFrameStored) != 0;
+    const uint64_t per = ((uint64_t)k + kFramesThreads - 1) / kFramesThreads;
+    const uint64_t f0 = t * per < k ? t * per : k;
+    const uint64_t f1 = f0 + per < k ? f0 + per : k;
+    const uint64_t bb = 1ull << block_bits;
+    uint64_t at[3] = {0, 0, 0};
+    for (uint64_t f = f0; f < f1; f++) {
+        const uint64_t c = content_bytes[f];
+        at[0] += c;
+        at[1] += frames_slot_bytes(c, block_bits, store);
+        at[2] += (c >> block_bits) + ((c & (bb - 1)) != 0 ? 1 : 0);
+    }
+    frames_scan_shares(at, shares);
+    for (uint64_t f = f0; f < f1; f++) {
+        const uint64_t c = content_bytes[f];
+        in_at[f] = at[0]; frame_at[f] = at[1]; base[f] = (uint32_t)at[2];
+        at[0] += c;
+        at[1] += frames_slot_bytes(c, block_bits, store);
+        at[2] += (c >> block_bits) + ((c & (bb - 1)) != 0 ? 1 : 0);
+    }
+    if (f1 == k && (f0 < f1 || t == 0)) { in_at[k] = at[0]; frame_at[k] = at[1]; base[k] = (uint32_t)at[2]; }
+}
+
+// encode, workgroup f: frame_plan_kernel for frame f's blocks, at their place in the batch's arrays (the contents lie
+// back to back, so a frame's last block ends where the next frame's first begins); the last frame closes both arrays
+__global__ __launch_bounds__(kFramesThreads)
+void frames_plan_kernel(const uint64_t* __restrict__ content_bytes, const uint64_t* __restrict__ in_at,
+                        const uint32_t* __restrict__ base, uint32_t k, uint32_t block_bits, uint64_t slab_bytes,
+                        uint64_t* __restrict__ in_off, uint64_t* __restrict__ slab_off) {
+    const uint32_t f = blockIdx.x;
+    if (f >= k) { return; }
+    const uint64_t g0 = base[f], n = base[f + 1] - base[f], at = in_at[f], c = content_bytes[f];
+    for (uint64_t b = threadIdx.x; b < n; b += kFramesThreads) {
+        in_off[g0 + b] = at + (b << block_bits);   // b < n: inside the content
+        slab_off[g0 + b] = (g0 + b) * slab_bytes;
+    }
+    if (f == k - 1 && threadIdx.x == 0) { in_off[g0 + n] = at + c; slab_off[g0 + n] = (g0 + n) * slab_bytes; }
+}
+
+// encode, workgroup f: frame_index_body for frame f at d_frames + frame_at[f] over its slice of the batch's arrays, then
+// the seal (frame_seal_kernel's arithmetic over the entries this workgroup has just written) and the dense offsets
+// once more, absolute in d_frames, for one compaction and one copy of stored blocks over the whole batch.
+// dense_rel: total blocks + k entries (frame f's n + 1 at base[f] + f), the body's own offsets from the frame's start
+__global__ __launch_bounds__(kFramesThreads)
+void frames_index_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
+                         const uint32_t* __restrict__ crc, const uint64_t* __restrict__ content_bytes,
+                         const uint64_t* __restrict__ frame_at, const uint32_t* __restrict__ base, uint32_t k,
+                         uint32_t win_bits, uint32_t block_bits, uint32_t flags, uint8_t* __restrict__ frames,
+                         uint64_t* __restrict__ copy_bytes, uint64_t* __restrict__ dense_rel,
+                         uint64_t* __restrict__ dense_off, uint32_t* __restrict__ stored,
+                         uint64_t* __restrict__ frame_bytes_out, int32_t* __restrict__ status_out) {
+    __shared__ uint64_t idx_range[2];              // the body's range for a checksum launch: not needed here
+    const uint32_t f = blockIdx.x;
+    if (f >= k) { return; }
+    const uint32_t t = threadIdx.x;
+    const uint64_t g0 = base[f];
+    const uint32_t n = base[f + 1] - base[f];
+    const uint64_t at = frame_at[f], capacity = frame_at[f + 1] - at, content = content_bytes[f];
+    uint8_t* const frame = frames + at;
+    uint64_t* const rel = dense_rel + g0 + f;
+    uint32_t* const mask = (flags & kFrameStored) != 0 ? stored + g0 : nullptr;
+    frame_index_body<false>(out_bytes + g0, err + g0, crc + g0, n, content, win_bits, block_bits, frame, capacity,
+                            copy_bytes + g0, rel, idx_range, frame_bytes_out + f, status_out + f,
+                            flags & kFrameStored, mask, 0u, nullptr);
+    __syncthreads();                               // the body's writes, lane 0's status among them
+    const bool ok = status_out[f] == 0;
+    const uint64_t per = ((uint64_t)n + 255) / 256;            // the body's shares: a lane sums the entries it wrote
+    const uint64_t b0 = t * per < n ? t * per : n;
+    const uint64_t b1 = b0 + per < n ? b0 + per : n;
+    const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
+    uint32_t r = 0;
+    for (uint64_t b = b0; b < b1; b++) {
+        dense_off[g0 + b] = ok ? at + rel[b] : 0;
+        if (ok) { r = crc_word(crc_word(r ^ index[2 * b]) ^ index[2 * b + 1]); }
+    }
+    uint32_t power;
+    const uint32_t idx_crc = index_crc_workgroup(r, b1 - b0, &power);
+    if (ok && t == 0) { reinterpret_cast<uint32_t*>(frame)[7] = gf_mul(crc32_small(frame, 28), power) ^ idx_crc; }
+    if (f == k - 1 && t == 0) { dense_off[g0 + n] = ok ? at + rel[n] : 0; }
+}
+
+// decode, one workgroup: base[f] = the blocks in front of frame f (k + 1 entries); frame f's entries start at
+// base[f] + f
+__global__ __launch_bounds__(kFramesThreads)
+void frames_decode_scan_kernel(const sqz_frames_item* __restrict__ items, uint32_t k, uint32_t* __restrict__ base) {
+    __shared__ uint64_t shares[1][kFramesThreads];
+    const uint32_t t = threadIdx.x;
+    const uint64_t per = ((uint64_t)k + kFramesThreads - 1) / kFramesThreads;
+    const uint64_t f0 = t * per < k ? t * per : k;
+    const uint64_t f1 = f0 + per < k ? f0 + per : k;
+    uint64_t at[1] = {0};
+    for (uint64_t f = f0; f < f1; f++) { at[0] += items[f].n_blocks; }
+    frames_scan_shares(at, shares);
+    for (uint64_t f = f0; f < f1; f++) { base[f] = (uint32_t)at[0]; at[0] += items[f].n_blocks; }
+    if (f1 == k && (f0 < f1 || t == 0)) { base[k] = (uint32_t)at[0]; }
+}
+
+// decode, workgroup f: the checksum of frame f's index, frame_open_body (versions 1 and 2, all blocks) over the
+// frame's n + 1 entries at base[f] + f, then the entries once more: in_off absolute in d_frames, out_off from out_base
+// (out_at[0]; the decode kernels address one uint32 slot per output byte by it), and skip.  Entry n is the pseudo-entry
+// frame_open_list_kernel has per slot: it reaches from the end of this frame's payload to the next frame's first
+// stream and is switched off.  A refused frame: its status, and every entry empty and switched off.  The last frame
+// closes both arrays.  The caller made sure that avail covers header and index.
+__global__ __launch_bounds__(kFramesThreads)
+void frames_open_kernel(const uint8_t* __restrict__ frames, const sqz_frames_item* __restrict__ items,
+                        const uint32_t* __restrict__ base, uint32_t k, uint64_t out_base,
+                        uint64_t* __restrict__ in_off, uint64_t* __restrict__ out_off, uint32_t* __restrict__ skip,
+                        uint32_t* __restrict__ stored, int32_t* __restrict__ status_out) {
+    __shared__ uint32_t idx_crc;
+    const uint32_t f = blockIdx.x;
+    if (f >= k) { return; }
+    const uint32_t t = threadIdx.x;
+    const uint64_t at = items[f].frame_at, avail = items[f].avail, content = items[f].content_bytes;
+    const uint64_t to = items[f].out_at - out_base;
+    const uint32_t n = items[f].n_blocks;
+    const uint64_t e0 = (uint64_t)base[f] + f;
+    const uint8_t* const frame = frames + at;
+    const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
+    const uint64_t per = ((uint64_t)n + 255) / 256;
+    const uint64_t b0 = t * per < n ? t * per : n;
+    const uint64_t b1 = b0 + per < n ? b0 + per : n;
+    uint32_t r = 0;
+    for (uint64_t b = b0; b < b1; b++) { r = crc_word(crc_word(r ^ index[2 * b]) ^ index[2 * b + 1]); }
+    uint32_t power;
+    const uint32_t c = index_crc_workgroup(r, b1 - b0, &power);
+    if (t == 0) { idx_crc = c; }
+    __syncthreads();
+    frame_open_body<false>(frame, avail, n, content, 0u, n, &idx_crc, in_off + e0, out_off + e0, status_out + f,
+                           stored + e0, 0u, nullptr, 0u);
+    __syncthreads();
+    const bool ok = status_out[f] == 0;
+    for (uint64_t j = t; j <= n; j += kFramesThreads) {
+        in_off[e0 + j] = ok ? at + in_off[e0 + j] : at;
+        out_off[e0 + j] = ok ? to + out_off[e0 + j] : to;
+        const uint32_t raw = j < n ? stored[e0 + j] : 0u;      // the body: all zeros on a refusal
+        stored[e0 + j] = raw;
+        skip[e0 + j] = ok && j < n ? raw : 1u;
+    }
+    __syncthreads();
+    if (f == k - 1 && t == 0) { in_off[e0 + n + 1] = in_off[e0 + n]; out_off[e0 + n + 1] = out_off[e0 + n]; }
+}
+
+// decode, workgroup f: frame_verify_kernel for frame f.  err: the decode chain's, one per ENTRY (block b of frame f at
+// base[f] + f + b); err_out: the caller's, one per BLOCK (at base[f] + b) -- the frame's status where it was refused,
+// EILSEQ where the decoder was content but the bytes are not the ones that were checksummed, else what the decoder said
+__global__ __launch_bounds__(kFramesThreads)
+void frames_verify_kernel(const uint8_t* __restrict__ frames, const sqz_frames_item* __restrict__ items,
+                          const uint32_t* __restrict__ base, uint32_t k, const uint32_t* __restrict__ crc,
+                          const int32_t* __restrict__ status, const int32_t* __restrict__ err,
+                          int32_t* __restrict__ err_out) {
+    const uint32_t f = blockIdx.x;
+    if (f >= k) { return; }
+    const uint64_t g0 = base[f], e0 = g0 + f;
+    const uint32_t n = items[f].n_blocks;
+    const int32_t st = status[f];
+    const uint32_t* const index = reinterpret_cast<const uint32_t*>(frames + items[f].frame_at + 32);
+    for (uint64_t b = threadIdx.x; b < n; b += kFramesThreads) {
+        int32_t e = st;
+        if (st == 0) {
+            e = err[e0 + b];
+            if (e == 0 && crc[e0 + b] != index[2 * b + 1]) { e = kErrEILSEQ; }
+        }
+        err_out[g0 + b] = e;
+    }
+}
+
+void launch_frames_encode_scan(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits, uint32_t flags,
+                               uint64_t* in_at, uint64_t* frame_at, uint32_t* base, hipStream_t stream) {
+    hipLaunchKernelGGL(frames_encode_scan_kernel, dim3(1), dim3(kFramesThreads), 0, stream, content_bytes, k,
+                       block_bits, flags, in_at, frame_at, base);
+}
+
+void launch_frames_plan(const uint64_t* content_bytes, const uint64_t* in_at, const uint32_t* base, uint32_t k,
+                        uint32_t block_bits, uint64_t slab_bytes, uint64_t* in_off, uint64_t* slab_off,
+                        hipStream_t stream) {
+    hipLaunchKernelGGL(frames_plan_kernel, dim3(k), dim3(kFramesThreads), 0, stream, content_bytes, in_at, base, k,
+                       block_bits, slab_bytes, in_off, slab_off);
+}
+
+void launch_frames_index(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc,
+                         const uint64_t* content_bytes, const uint64_t* frame_at, const uint32_t* base, uint32_t k,
+                         uint32_t win_bits, uint32_t block_bits, uint32_t flags, uint8_t* frames, uint64_t* copy_bytes,
+                         uint64_t* dense_rel, uint64_t* dense_off, uint32_t* stored, uint64_t* frame_bytes_out,
+                         int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frames_index_kernel, dim3(k), dim3(kFramesThreads), 0, stream, out_bytes, err, crc,
+                       content_bytes, frame_at, base, k, win_bits, block_bits, flags, frames, copy_bytes, dense_rel,
+                       dense_off, stored, frame_bytes_out, status_out);
+}
+
+void launch_frames_decode_scan(const sqz_frames_item* items, uint32_t k, uint32_t* base, hipStream_t stream) {
+    hipLaunchKernelGGL(frames_decode_scan_kernel, dim3(1), dim3(kFramesThreads), 0, stream, items, k, base);
+}
+
+void launch_frames_open(const uint8_t* frames, const sqz_frames_item* items, const uint32_t* base, uint32_t k,
+                        uint64_t out_base, uint64_t* in_off, uint64_t* out_off, uint32_t* skip, uint32_t* stored,
+                        int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frames_open_kernel, dim3(k), dim3(kFramesThreads), 0, stream, frames, items, base, k, out_base,
+                       in_off, out_off, skip, stored, status_out);
+}
+
+void launch_frames_verify(const uint8_t* frames, const sqz_frames_item* items, const uint32_t* base, uint32_t k,
+                          const uint32_t* crc, const int32_t* status, const int32_t* err, int32_t* err_out,
+                          hipStream_t stream) {
+    hipLaunchKernelGGL(frames_verify_kernel, dim3(k), dim3(kFramesThreads), 0, stream, frames, items, base, k, crc,
+                       status, err, err_out);
+}
+
 } // namespace sqzk

@@ -263,4 +263,37 @@ void launch_frame_append_index(const uint8_t* old, uint32_t n_blocks, uint64_t c
                                uint64_t* seg_dst, uint64_t* seg_src, uint64_t* seg_len, uint64_t* idx_off,
                                uint64_t* frame_bytes_out, int32_t* status, hipStream_t stream);
 
+// k frames in one call (frame.hip, "batches of frames"): a workgroup per frame, launches that do
+// not depend on k.  base[f] (k + 1 entries) = the blocks in front of frame f.
+// encode_scan: from the k sizes in_at (the contents lie back to back), frame_at (the bounds of sqz_frame_bound_ex,
+//   each rounded up to 16) and base, k + 1 entries each.
+// plan: launch_frame_plan for every frame's blocks at base[f] of in_off / slab_off (total blocks + 1 entries).
+// index: launch_frame_index / _v2 for frame f at frames + frame_at[f] over its slice of out_bytes, err, crc, copy_bytes,
+//   stored (null without SQZ_FRAME_STORED), frame_bytes_out[f] and status_out[f]; the index checksum and the seal in
+//   the same workgroup; dense_off (total blocks + 1) absolute in `frames` for ONE launch_compact_blocks and ONE
+//   launch_range_copy over the batch.  dense_rel: total blocks + k entries of room.
+// decode_scan: base from items[].n_blocks.
+// open: launch_frame_open_v2 (all blocks) for frame f over its n + 1 ENTRIES at base[f] + f of in_off / out_off (total
+//   blocks + k + 1 entries; in_off absolute in `frames`, out_off = out_at[f] - out_base + the block's place), skip and
+//   stored (total blocks + k); entry n of a frame is switched off and reaches to the next frame's first stream.  The
+//   index checksum is taken in the same workgroup.  A refused frame: status_out[f], every entry empty and switched off.
+// verify: launch_frame_verify for every frame; err by entry in, err_out by block (at base[f]) out.
+void launch_frames_encode_scan(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits, uint32_t flags,
+                               uint64_t* in_at, uint64_t* frame_at, uint32_t* base, hipStream_t stream);
+void launch_frames_plan(const uint64_t* content_bytes, const uint64_t* in_at, const uint32_t* base, uint32_t k,
+                        uint32_t block_bits, uint64_t slab_bytes, uint64_t* in_off, uint64_t* slab_off,
+                        hipStream_t stream);
+void launch_frames_index(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc,
+                         const uint64_t* content_bytes, const uint64_t* frame_at, const uint32_t* base, uint32_t k,
+                         uint32_t win_bits, uint32_t block_bits, uint32_t flags, uint8_t* frames, uint64_t* copy_bytes,
+                         uint64_t* dense_rel, uint64_t* dense_off, uint32_t* stored, uint64_t* frame_bytes_out,
+                         int32_t* status_out, hipStream_t stream);
+void launch_frames_decode_scan(const sqz_frames_item* items, uint32_t k, uint32_t* base, hipStream_t stream);
+void launch_frames_open(const uint8_t* frames, const sqz_frames_item* items, const uint32_t* base, uint32_t k,
+                        uint64_t out_base, uint64_t* in_off, uint64_t* out_off, uint32_t* skip, uint32_t* stored,
+                        int32_t* status_out, hipStream_t stream);
+void launch_frames_verify(const uint8_t* frames, const sqz_frames_item* items, const uint32_t* base, uint32_t k,
+                          const uint32_t* crc, const int32_t* status, const int32_t* err, int32_t* err_out,
+                          hipStream_t stream);
+
 } // namespace sqzk

@@ -22,6 +22,7 @@ of its N-byte elements, then all second bytes, and so on -- which is what arrays
 figures; noise gains nothing and a few inputs lose a little, so it is opt-in).  The readers pick the version up from
 the header.  Not together with a dictionary; gather, update and append do not take version 4 yet.
 """
+import collections
 import ctypes as C
 import errno
 
@@ -637,6 +638,227 @@ def append_frame(d_frame, data, d_out=None, info: dict = None, dictionary=None, 
     else:
         _raise(L.sqz_hip_frame_append(*head, *tail), "sqz_hip_frame_append")
     return d_out, frame_bytes, blocks_encoded, status
+
+
+# ---- many frames in one call ("Batches of frames") ------------------------
+def _frames_sizes(sizes, who):
+    host = [int(v) for v in sizes]
+    if any(v < 0 or v >> 62 for v in host):
+        raise ValueError(f"{who}: sizes must be 0 .. 2^62 - 1")
+    return host
+
+
+def _frames_bits(win_bits, block_bits, who):
+    if isinstance(block_bits, bool) or not isinstance(block_bits, int) or not 12 <= block_bits <= 24:
+        raise ValueError(f"{who}: block_bits must be 12 .. 24, not {block_bits!r}")
+    if win_bits is not None and (isinstance(win_bits, bool) or not isinstance(win_bits, int) or not 10 <= win_bits <= 15):
+        raise ValueError(f"{who}: win_bits must be 10 .. 15, not {win_bits!r}")
+
+
+_host_tables = collections.deque(maxlen=64)
+
+
+def _pinned(array):
+    """a numpy array's bytes in page-locked host memory, for a copy the stream makes later: the call returns before
+    the copy has run, so the last tables are kept alive here rather than by the caller"""
+    import numpy as np
+    import torch
+    table = torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1).copy()).pin_memory()
+    _host_tables.append(table)
+    return table
+
+
+def frames_bound(sizes, block_bits: int = 18, store: bool = False):
+    """Where encode_frames puts the frames of contents of `sizes` bytes: (total, frame_at) -- frame f starts at
+    frame_at[f], a multiple of 16, and has its worst-case size (frame_bound) of room; total is the size of the
+    buffer.  Host code: no device is touched."""
+    host = _frames_sizes(sizes, "frames_bound")
+    _frames_bits(None, block_bits, "frames_bound")
+    k = len(host)
+    arr = (C.c_uint64 * max(k, 1))(*host)
+    at = (C.c_uint64 * (k + 1))()
+    total = int(N.lib().sqz_hip_frames_bound(arr, k, block_bits, _flags(store), at))
+    if total == 0 and k > 0:
+        raise ValueError("frames_bound: the sizes add up to more than a batch holds")
+    return total, [int(v) for v in at[:k]]
+
+
+def encode_frames(d_in, sizes, win_bits: int = 15, block_bits: int = 18, store: bool = False, parse: str = "greedy",
+                  d_out=None, scratch=None):
+    """Many frames in one call: the contents lie back to back in d_in (uint8), sizes[f] bytes each, and frame f is
+    written at d_frames[frame_at[f]:] -- byte for byte the frame FrameEncoder writes for that content alone with the
+    same arguments (versions 1 and 2).  The launches do not depend on the number of frames.
+    Enqueues and returns (d_frames, frame_at, d_frame_bytes int64[k], d_err int32[total blocks], d_status int32[k]):
+    frame_at is frames_bound()'s host list, everything else device tensors to read after a synchronise.  Frame f is
+    d_frames[frame_at[f] : frame_at[f] + d_frame_bytes[f]] when d_status[f] is 0; a frame with a failed block has
+    that block's errno there and is not written, which costs its neighbours nothing.  The bytes between two frames are
+    not touched.  d_out: a uint8 tensor of at least frames_bound()'s total, made when not given."""
+    import numpy as np
+    import torch
+    code = parse_code(parse)
+    host = _frames_sizes(sizes, "encode_frames")
+    _frames_bits(win_bits, block_bits, "encode_frames")
+    L = N.lib()
+    k = len(host)
+    total, frame_at = frames_bound(host, block_bits, store)
+    if d_in.dtype != torch.uint8 or d_in.dim() != 1 or d_in.numel() < sum(host):
+        raise ValueError("encode_frames: d_in must be a one-dimensional uint8 tensor that holds all the contents")
+    device = d_in.device
+    if d_out is None:
+        d_out = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
+    elif d_out.dtype != torch.uint8 or d_out.numel() < total:
+        raise ValueError("encode_frames: d_out must be a uint8 tensor of at least frames_bound()'s total")
+    blocks = sum((v + (1 << block_bits) - 1) >> block_bits for v in host)
+    frame_bytes = torch.zeros(max(k, 1), dtype=torch.int64, device=device)
+    status = torch.zeros(max(k, 1), dtype=torch.int32, device=device)
+    err = torch.zeros(max(blocks, 1), dtype=torch.int32, device=device)
+    table = _pinned(np.asarray(host, np.uint64)) if k > 0 else None
+    if scratch is None:
+        need = int(L.sqz_hip_frames_encode_scratch_bytes(_ptr(table), k, block_bits, _flags(store)))
+        scratch = _scratch_for(device, max(need, 16))
+    _raise(L.sqz_hip_frames_encode(_ptr(d_in), _ptr(table), k, win_bits, block_bits, _flags(store), code, _ptr(d_out),
+                                   d_out.numel(), _ptr(frame_bytes), _ptr(status), _ptr(err), _ptr(scratch),
+                                   scratch.numel(), _stream()), "sqz_hip_frames_encode")
+    return d_out, frame_at, frame_bytes[:k], err[:blocks], status[:k]
+
+
+def _headers_dev(d_frames, frame_at):
+    """the 32-byte headers of the frames at frame_at, read back from the device in one copy"""
+    import torch
+    at = torch.tensor(frame_at, dtype=torch.int64, device=d_frames.device)
+    idx = at[:, None] + torch.arange(HEADER_BYTES, device=d_frames.device)[None, :]
+    raw = d_frames[idx.reshape(-1)].cpu().numpy().tobytes()
+    return [raw[HEADER_BYTES * f:HEADER_BYTES * (f + 1)] for f in range(len(frame_at))]
+
+
+def _info_or_nothing(header: bytes):
+    """frame_info() of a header, or the figures of an empty frame for a header that does not parse: the device
+    refuses such a frame by the same checks, and alone"""
+    try:
+        return frame_info(header)
+    except SqzError:
+        return {"n_blocks": 0, "content_bytes": 0}
+
+
+def decode_frames(d_frames, frame_at, infos=None, d_out=None, out_at=None, scratch=None):
+    """Many device-resident frames in one call: frame f lies at d_frames[frame_at[f]:] (frame_at: ascending multiples
+    of 16; a frame reaches at most to the next one, the last to the end of the tensor), any mix of versions 1 and 2,
+    each with its own win_bits and block_bits.  infos: a list of frame_info() dicts of the headers; without it the
+    headers are read back from the device in one copy.  Frame f's content goes to d_out[out_at[f]:]; out_at defaults
+    to the contents packed back to back (gaps are allowed and stay untouched, but cost scratch), d_out is made when
+    not given.  The launches do not depend on the number of frames.
+    Enqueues and returns (d_out, out_at, d_err int32[total blocks], d_status int32[k]); frame f's blocks are
+    d_err[sum(n_blocks[:f]):].  A frame that is refused (a header or index that does not hold; version 3 or 4: EINVAL)
+    has its status in d_status[f] and in all its d_err, and nothing of its output is written; a block whose checksum
+    does not hold is EILSEQ in d_err.  Either costs the other frames nothing."""
+    import numpy as np
+    import torch
+    frame_at = [int(v) for v in frame_at]
+    k = len(frame_at)
+    if any(v < 0 or v % 16 != 0 for v in frame_at):
+        raise ValueError("decode_frames: every frame_at must be a multiple of 16")
+    if infos is not None and len(infos) != k:
+        raise ValueError("decode_frames: as many infos as frame_at")
+    if out_at is not None and len(out_at) != k:
+        raise ValueError("decode_frames: as many out_at as frame_at")
+    if d_frames.dtype != torch.uint8 or d_frames.dim() != 1:
+        raise ValueError("decode_frames: d_frames must be a one-dimensional uint8 tensor")
+    if any(b <= a for a, b in zip(frame_at, frame_at[1:])) or (k > 0 and frame_at[-1] >= max(d_frames.numel(), 1)):
+        raise ValueError("decode_frames: frame_at must be ascending and inside d_frames")
+    L = N.lib()
+    device = d_frames.device
+    if infos is None:
+        infos = [_info_or_nothing(h) for h in _headers_dev(d_frames, frame_at)] if k > 0 else []
+    sizes = [int(i["content_bytes"]) for i in infos]
+    counts = [int(i["n_blocks"]) for i in infos]
+    if out_at is None:
+        out_at = [sum(sizes[:f]) for f in range(k)]
+    out_at = [int(v) for v in out_at]
+    end = max([o + s for o, s in zip(out_at, sizes)], default=0)
+    if d_out is None:
+        d_out = torch.empty(max(end, 1), dtype=torch.uint8, device=device)
+    elif d_out.dtype != torch.uint8 or d_out.numel() < end:
+        raise ValueError("decode_frames: d_out must be a uint8 tensor that holds every output")
+    ends = frame_at[1:] + [d_frames.numel()]
+    items = np.zeros(max(k, 1), np.dtype([("frame_at", "<u8"), ("avail", "<u8"), ("content_bytes", "<u8"),
+                                          ("out_at", "<u8"), ("n_blocks", "<u4"), ("zero", "<u4")]))
+    for f in range(k):
+        items[f] = (frame_at[f], ends[f] - frame_at[f], sizes[f], out_at[f], counts[f], 0)
+    table = _pinned(items) if k > 0 else None
+    blocks = sum(counts)
+    err = torch.zeros(max(blocks, 1), dtype=torch.int32, device=device)
+    status = torch.zeros(max(k, 1), dtype=torch.int32, device=device)
+    if k > 0:
+        if scratch is None:
+            need = int(L.sqz_hip_frames_decode_scratch_bytes(_ptr(table), k))
+            if need == 0:
+                raise ValueError("decode_frames: frames or outputs that are not ascending and disjoint")
+            scratch = _scratch_for(device, need)
+        _raise(L.sqz_hip_frames_decode(_ptr(d_frames), _ptr(table), k, _ptr(d_out), _ptr(err), _ptr(status),
+                                       _ptr(scratch), scratch.numel(), _stream()), "sqz_hip_frames_decode")
+    return d_out, out_at, err[:blocks], status[:k]
+
+
+def compress_frames(datas, win_bits: int = 15, block_bits: int = 18, store: bool = False,
+                    parse: str = "greedy") -> list:
+    """compress_frame() of every item of `datas` (versions 1 and 2) in one device call: one upload, one synchronise,
+    one download.  Raises SqzError naming the first frame that failed."""
+    import torch
+    parse_code(parse)                                        # argument errors before anything is uploaded
+    _frames_bits(win_bits, block_bits, "compress_frames")
+    datas = [bytes(d) for d in datas]
+    if not datas:
+        return []
+    blob = b"".join(datas)
+    d_in = torch.frombuffer(bytearray(blob or b"\0"), dtype=torch.uint8)[:len(blob)].to("cuda")
+    d_frames, frame_at, frame_bytes, _, status = encode_frames(d_in, [len(d) for d in datas], win_bits, block_bits,
+                                                               store, parse)
+    torch.cuda.synchronize()
+    sizes, states = frame_bytes.cpu().tolist(), status.cpu().tolist()
+    for f, st in enumerate(states):
+        if st != 0:
+            raise SqzError(st, f"compress_frames: frame {f}: {errno.errorcode.get(st, st)}")
+    host = d_frames.cpu().numpy()
+    return [host[a:a + n].tobytes() for a, n in zip(frame_at, sizes)]
+
+
+def decompress_frames(frames, return_errors: bool = False):
+    """decompress_frame() of every item of `frames` (versions 1 and 2, any mix of parameters) in one device call: one
+    upload, one synchronise, one download.  Raises SqzError naming the first frame that did not hold -- its status, or
+    its first failed block -- unless return_errors is set: then (contents, errors) with errors[f] = (status,
+    block_errors); good frames and good blocks are delivered, a refused frame is b""."""
+    import numpy as np
+    import torch
+    frames = [bytes(f) for f in frames]
+    if not frames:
+        return ([], []) if return_errors else []
+    infos = [_info_or_nothing(f[:HEADER_BYTES]) if len(f) >= HEADER_BYTES else {"n_blocks": 0, "content_bytes": 0}
+             for f in frames]
+    frame_at, at = [], 0
+    for f in frames:
+        frame_at.append(at)
+        at += (max(len(f), HEADER_BYTES) + 15) & ~15
+    image = np.zeros(at + 16, np.uint8)
+    for a, f in zip(frame_at, frames):
+        image[a:a + len(f)] = np.frombuffer(f, np.uint8)
+    d_frames = torch.from_numpy(image)[:at].to("cuda")
+    d_out, out_at, err, status = decode_frames(d_frames, frame_at, infos)
+    torch.cuda.synchronize()
+    host, errs, states = d_out.cpu().numpy(), err.cpu().tolist(), status.cpu().tolist()
+    contents, errors, b0 = [], [], 0
+    for f, info in enumerate(infos):
+        n = info["n_blocks"]
+        block_errors = errs[b0:b0 + n]
+        b0 += n
+        st = states[f]
+        if not return_errors and (st != 0 or any(block_errors)):
+            first = st if st != 0 else next(e for e in block_errors if e != 0)
+            e = SqzError(first, f"decompress_frames: frame {f}: {errno.errorcode.get(first, first)}")
+            e.frame, e.block_errors = f, block_errors
+            raise e
+        contents.append(b"" if st != 0 else host[out_at[f]:out_at[f] + info["content_bytes"]].tobytes())
+        errors.append((st, block_errors))
+    return (contents, errors) if return_errors else contents
 
 
 def _append_file(frame: bytes, data: bytes, dictionary, parse: str) -> bytes:
