@@ -396,7 +396,7 @@ void entropy_decode_kernel(const uint8_t* __restrict__ in,
         int done = 0;
         ST_SEC(2)
         lds_fence();                                          // the slots are in registers: their space is the batch's now
-        if (m > 0) { done = bump_batch<false>(&lds.tree, nullptr, lit, pos, lane, m, a_v, b_v, ca, wa, cb, wb); }
+        if (m > 0) { done = bump_batch<false, false>(&lds.tree, nullptr, lit, pos, lane, m, a_v, b_v, ca, wa, cb, wb); }
         ST_SEC(3)
         uint64_t resume = bit0;
         if (done > 0) {
@@ -933,7 +933,7 @@ void entropy_decode_mw_kernel(const uint8_t* __restrict__ in,
 #ifdef SQZ_STATS
         mw_steps++;
 #endif
-        if (m > 0) { done = bump_batch<false>(&lds.tree, nullptr, lit, pos, lane, m, a_v, b_v, ca, wa, cb, wb); }
+        if (m > 0) { done = bump_batch<false, false>(&lds.tree, nullptr, lit, pos, lane, m, a_v, b_v, ca, wa, cb, wb); }
         MW_SEC(7)
 #ifdef SQZ_STATS
         mw_done += (uint32_t)done;

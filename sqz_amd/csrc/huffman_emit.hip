@@ -13,7 +13,10 @@
 // part in the batched frequency update of sqz_tree.h (bump_batch); the tokens in front of the
 // first one whose update could restructure a tree are applied and their bits -- code, extra bits,
 // code, extra bits -- are packed in parallel (prefix sum of the widths, LDS atomic OR into a bit
-// image) and leave as whole 8-byte words, coalesced.  The token a step stops at (a restructure,
+// image).  The image lives in LDS from one step to the next (TreeLds::P64; the batch's histogram
+// lives in pend + lvl here): a step deposits behind what the image holds, and the whole 8-byte words
+// leave together, coalesced, when the next step might not fit, at the end of the stream, and at
+// once where they would pass the capacity.  The token a step stops at (a restructure,
 // an unseen symbol with its NYT escape) takes the one-at-a-time path: lane k = level k of the
 // chain, code = one __ballot("am I the hi child?"), the reference's own swap / promote tests,
 // restructuring on the whole wave; its bits wait in a register and ride along with the next
@@ -29,24 +32,52 @@ namespace sqzk {
 constexpr int kPendBits = 58;         // most bits the pending register hands to a pack
 
 struct EmitLds {
-    TreeLds  tree;                    // tree.P64 doubles as the bit image of a pack (stream order = MSB first)
+    TreeLds  tree;                    // tree.P64 is the bit image (stream order = MSB first); the histogram is in tree.pend + lvl
     uint32_t code[kCodeSlots];
 };
 
+constexpr uint32_t kImageBits = 64u * (uint32_t)kImageWords;
+// the worst single step still fits behind what a drain leaves: 63 carried bits, the pending register, 64 tokens
+static_assert(63 + kPendBits + kWave * kTokenBits < (int)kImageBits, "a step's bits fit the image after a drain");
+
+#ifdef SQZ_WAVE_EMU
+static unsigned g_dbg_drains, g_dbg_steps;    // emulator builds only: drains of the bit image, steps of the main loop
+#endif
+
+// (stats build: the pack's own sections, block 1: 24 scan + deposits, 25 zeroing, 26 stores / drains, 27 carry read-back)
+#if defined(SQZ_STATS) && defined(SQZ_SEC_TIMERS)
+#define PK_BEGIN uint64_t pk_t_ = __builtin_readcyclecounter();
+#define PK(k) { const uint64_t n_ = __builtin_readcyclecounter(); if (blockIdx.x == 1 && threadIdx.x == 0) { g_sec[k] += n_ - pk_t_; g_secn[k]++; } pk_t_ = n_; }
+#else
+#define PK_BEGIN
+#define PK(k)
+#endif
 
 struct BitQueue {
     EmitLds* lds;
     uint8_t* out;        // global
     uint64_t capacity;
-    uint64_t bytes;      // bytes produced so far (as the reference counts them)
-    uint64_t carry_v;    // the bits of the last partial word, left-aligned (what image[0] starts as)
-    int      carry;      // how many (0..63)
+    uint64_t bytes;      // bytes that have left the image (as the reference counts them)
+    // The image (tree.P64) is the stream from byte `bytes` on, MSB first: its first `fill` bits are valid, every
+    // bit behind them is zero.  It lives from step to step; whole words leave when the next step might not fit
+    // (drain), at the end, and at once when they would pass the capacity (so that the error is raised in the
+    // step in which the reference's bit writer raises it).
+    uint32_t fill;
     int      error;
     // bits of the one-at-a-time path waiting for the next pack: the low pend_n bits of pend_v,
     // first-out bit on top.  They ride along with the next batch instead of costing a pack of
     // their own (most steps end with one such token).
     uint64_t pend_v;
     int      pend_n;
+
+    // an empty image with the header bits that precede the payload (single-stream API) in front
+    __device__ __forceinline__ void start(uint64_t prefix_acc, int prefix_fill, int lane) {
+        for (int k = lane; k < kImageWords; k += kWave) {
+            lds->tree.P64[k] = (k == 0 && prefix_fill > 0) ? (prefix_acc << (64 - prefix_fill)) : 0ull;
+        }
+        lds_fence();
+        fill = (uint32_t)prefix_fill;
+    }
 
     // store 8-byte words [0, words) of the image (bitstream.h:33-43)
     __device__ __forceinline__ void store_words(int words, int lane) {
@@ -67,6 +98,29 @@ struct BitQueue {
         else { bytes = capacity; error = kE2BIG; }
     }
 
+    // the full words leave, the partial word moves to the front, the words it came from are zero again
+    __device__ __forceinline__ void drain(int lane) {
+        const int words = (int)(fill >> 6);
+        if (words == 0) { return; }
+#ifdef SQZ_WAVE_EMU
+        if (lane == 0) { g_dbg_drains++; }
+#endif
+        store_words(words, lane);
+        const uint64_t part = lds->tree.P64[words];         // (zero when fill is a multiple of 64; words < kImageWords)
+        lds_fence();
+        for (int k = lane; k <= words; k += kWave) { lds->tree.P64[k] = (k == 0) ? part : 0ull; }
+        lds_fence();
+        fill &= 63u;
+    }
+
+    // after a deposit: words that would pass the capacity leave now (store_words raises kE2BIG and stops at
+    // the capacity, in the step in which a word-by-word writer would have)
+    __device__ __forceinline__ void settle(uint32_t added, int lane) {
+        fill += added;
+        pend_v = 0; pend_n = 0;
+        if (error == 0 && (uint64_t)(fill >> 6) * 8 > capacity - bytes) { drain(lane); }
+    }
+
     // n bits of v (first-out bit = most significant of the n) at stream bit o of the image
     __device__ __forceinline__ void deposit(uint64_t v, uint32_t n, uint32_t o) {
         const uint32_t w = o >> 6, s = o & 63u;
@@ -83,30 +137,31 @@ struct BitQueue {
     }
 
     // the pending bits, then every lane's two fields (n1 then n2 bits, each 0..38, first-out bit =
-    // most significant): prefix sum of the widths, LDS atomic OR into the image behind the carried
-    // bits, full words leave for HBM
+    // most significant): prefix sum of the widths, LDS atomic OR into the image behind what it holds
     __device__ __forceinline__ void pack_lanes(uint64_t v1, uint32_t n1, uint64_t v2, uint32_t n2, int lane) {
-        for (int k = lane; k < kImageWords; k += kWave) { lds->tree.P64[k] = (k == 0) ? carry_v : 0ull; }
-        lds_fence();
+        PK_BEGIN
         const uint32_t incl = wave_scan(n1 + n2);
-        const uint32_t head = (uint32_t)carry + (uint32_t)pend_n;
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1) + head;
-        if (pend_n != 0 && lane == 0) { deposit(pend_v, (uint32_t)pend_n, (uint32_t)carry); }
-        const uint32_t at = head + incl - (n1 + n2);
+        const uint32_t added = (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1) + (uint32_t)pend_n;
+        PK(24)
+        if (fill + added >= kImageBits) { drain(lane); }
+        PK(26)
+        if (pend_n != 0 && lane == 0) { deposit(pend_v, (uint32_t)pend_n, fill); }
+        const uint32_t at = fill + (uint32_t)pend_n + incl - (n1 + n2);
         if (n1 != 0) { deposit(v1, n1, at); }
         if (n2 != 0) { deposit(v2, n2, at + n1); }
         lds_fence();
-        const int words = (int)(total >> 6);
-        store_words(words, lane);
-        carry_v = uni64(lds->tree.P64[words]);             // partial word becomes the new carry
-        lds_fence();
-        carry = (int)(total & 63u);
-        pend_v = 0; pend_n = 0;
+        PK(24)
+        settle(added, lane);
+        PK(26)
     }
 
     // what is pending, alone (the register is full, or the stream ends)
     __device__ __forceinline__ void pack(int lane) {
-        if (pend_n != 0) { pack_lanes(0ull, 0u, 0ull, 0u, lane); }
+        if (pend_n == 0) { return; }
+        if (fill + (uint32_t)pend_n >= kImageBits) { drain(lane); }
+        if (lane == 0) { deposit(pend_v, (uint32_t)pend_n, fill); }
+        lds_fence();
+        settle((uint32_t)pend_n, lane);
     }
 
     // value's low `width` bits, first-out bit = most significant; width 1..32
@@ -129,14 +184,16 @@ struct BitQueue {
         push32(__brev(value) >> (32 - width), width, lane);
     }
 
-    __device__ __forceinline__ void flush(int lane) {       // bitstream.h:112-114
+    // the stream ends: the last partial word leaves as a whole one (bitstream.h:112-114)
+    __device__ __forceinline__ void flush(int lane) {
         pack(lane);
-        if (carry > 0) {
-            if (lane == 0) { lds->tree.P64[0] = carry_v; }
-            lds_fence();
-            store_words(1, lane);
-            carry = 0; carry_v = 0;
-        }
+        drain(lane);
+        if (fill != 0) { fill = 64u; drain(lane); }
+    }
+    // the stream is given up (an error): what is pending and the full words leave, the partial word does not
+    __device__ __forceinline__ void abandon(int lane) {
+        pack(lane);
+        drain(lane);
     }
 };
 
@@ -255,10 +312,8 @@ void huffman_emit_kernel(const uint32_t* __restrict__ tokens,
     q.bytes = 0;
     q.pend_v = 0;
     q.pend_n = 0;
-    // header bits that precede the payload (single-stream API): the carry
-    q.carry = prefix_fill;
-    q.carry_v = prefix_fill > 0 ? (prefix_acc << (64 - prefix_fill)) : 0ull;
     q.error = 0;
+    q.start(prefix_acc, prefix_fill, lane);
     int err = 0;
 
     if (too_many) { err = kEINVAL; }
@@ -339,7 +394,7 @@ void huffman_emit_kernel(const uint32_t* __restrict__ tokens,
         int wa = 0, wb = 0;
         const int offered = m;
         ES(0)
-        if (m >= 1 && !frozen) { m = bump_batch<true>(&lds.tree, lds.code, lit, pos, lane, m, a, bsym, ca, wa, cb, wb); }
+        if (m >= 1 && !frozen) { m = bump_batch<true, true>(&lds.tree, lds.code, lit, pos, lane, m, a, bsym, ca, wa, cb, wb); }
         else { m = 0; }
         ES(1)
         if (m >= 1) {
@@ -389,6 +444,9 @@ void huffman_emit_kernel(const uint32_t* __restrict__ tokens,
 #ifdef SQZ_STATS
         es_steps++;
 #endif
+#ifdef SQZ_WAVE_EMU
+        if (lane == 0) { g_dbg_steps++; }
+#endif
         {
             avg4 += (int)(cursor - step_start) - (avg4 >> 2);
             want = ((avg4 * 3) >> 3) + 6;
@@ -419,7 +477,7 @@ void huffman_emit_kernel(const uint32_t* __restrict__ tokens,
     }
 #endif
     if (err == 0) { q.flush(lane); err = q.error; }
-    else { q.pack(lane); }
+    else { q.abandon(lane); }
     if (lane == 0) {
         out_bytes[b] = q.bytes;
         err_out[b] = err;
@@ -464,8 +522,8 @@ __device__ __forceinline__ void debug_drive(T& t, DbgLit& lit, DbgPos& pos, Emit
         const bool frozen = t.complete != 0 || t.depth >= kFreezeDepth || t.aux == 0;
         uint32_t ca, cb; int wa, wb;
         if (m > 0 && !frozen) {
-            m = is_pos ? bump_batch<true>(&lds.tree, lds.code, lit, pos, lane, m, -1, leaf, ca, wa, cb, wb)
-                       : bump_batch<true>(&lds.tree, lds.code, lit, pos, lane, m, leaf, -1, ca, wa, cb, wb);
+            m = is_pos ? bump_batch<true, true>(&lds.tree, lds.code, lit, pos, lane, m, -1, leaf, ca, wa, cb, wb)
+                       : bump_batch<true, true>(&lds.tree, lds.code, lit, pos, lane, m, leaf, -1, ca, wa, cb, wb);
         } else { m = 0; }
         k += (uint32_t)m;
         if (k < count) {                                       // the symbol the batch stopped at, exactly

@@ -76,6 +76,8 @@
 // significant of `depth` bits), valid while the tree is shallower than kAuxDepth.
 #pragma once
 
+#include <cstddef>
+
 #include "sqz_device.h"
 
 namespace sqzk {
@@ -142,6 +144,10 @@ __device__ unsigned int g_secn[32];
 #define XSEC(k)
 #endif
 
+// the histogram words as the encoder reaches them (over pend + lvl, which have types of their own)
+typedef uint64_t __attribute__((may_alias)) hist_u64;
+typedef uint32_t __attribute__((may_alias)) hist_u32;
+
 struct TreeLds {
     uint32_t lnk[kAllNodes];
     uint32_t rng[kAllNodes];
@@ -149,9 +155,30 @@ struct TreeLds {
     uint32_t pend[kWave];                     // parent << 16 | child, one per pending level
     uint16_t lvl[kStack];                     // the one-lane path's stack
     // one batch: histogram over leaf positions (a byte each), turned into its prefix sums in place
-    // (the first 64 words); the encoder's bit image of a step lives here too, after the update
+    // (the first 64 words).  The decoders keep it here; the encoder's bit image lives here, from one
+    // step to the next, and its histogram in pend + lvl (hist64 / hist32 / hist8 below)
     union { uint64_t P64[kImageWords]; uint32_t P32[2 * kImageWords]; uint8_t P8[8 * kImageWords]; };
+
+    // Where bump_batch counts.  kInPend (the encoder, the tree entry): the 64 words that start at pend.  Neither
+    // pend nor lvl carries anything from one step to the next there: pend is the climb's stack inside one exact
+    // update (its slots 61-63 the counters of one slow call), lvl the one-lane path's stack.  The decoders' pend
+    // slots 57-60 live between steps, so they count in P64.  (A lane without a token reads byte 8 * kWave of
+    // the histogram, one past its end, and drops what it read: word 0 of P64 in the encoder.)
+    template <bool kInPend> __device__ __forceinline__ auto* hist64() {
+        if constexpr (kInPend) { return reinterpret_cast<hist_u64*>(pend); } else { return &P64[0]; }
+    }
+    template <bool kInPend> __device__ __forceinline__ auto* hist32() {
+        if constexpr (kInPend) { return reinterpret_cast<hist_u32*>(pend); } else { return &P32[0]; }
+    }
+    template <bool kInPend> __device__ __forceinline__ uint8_t* hist8() {
+        if constexpr (kInPend) { return reinterpret_cast<uint8_t*>(pend); } else { return &P8[0]; }
+    }
 };
+static_assert(offsetof(TreeLds, lvl) == offsetof(TreeLds, pend) + sizeof(uint32_t) * kWave, "pend and lvl are contiguous");
+static_assert(offsetof(TreeLds, pend) % 8 == 0, "the histogram's 64-bit words are aligned");
+static_assert(sizeof(uint32_t) * kWave + sizeof(uint16_t) * kStack >= 8 * (size_t)kWave, "clear_histogram writes one word per lane");
+static_assert(8 * kWave >= kPositions + 1, "a prefix sum per leaf position and one behind the last (41 words)");
+static_assert(offsetof(TreeLds, P64) == offsetof(TreeLds, pend) + 8 * (size_t)kWave, "the byte behind the encoder's histogram is the image's");
 
 // huffman.h:29-33 + squeeze.h:397-403, kept only by the kernels' kStats instantiation
 struct TreeStats { uint32_t updates, swaps, moves; };
@@ -1302,7 +1329,8 @@ template <bool CODES, bool STATS> using PosTreeT = Tree<kPosBase, kPosLeaves, kP
 // Returns how many leading tokens were applied (0..m).  code_a/depth_a/code_b/depth_b are the
 // static tree's and valid for all m lanes (kWantCode: the encoder emits them, the decoder has no
 // use for them).  Only callable while both trees keep their positions (aux) and take updates.
-template <bool kWantCode, class LIT, class POS>
+// kHistInPend: where the histogram lives (TreeLds::hist64): the encoder's P64 is its bit image.
+template <bool kWantCode, bool kHistInPend, class LIT, class POS>
 __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, const LIT& lit, const POS& pos,
                                           int lane, int m, int a, int b,
                                           uint32_t& code_a, int& depth_a, uint32_t& code_b, int& depth_b) {
@@ -1368,21 +1396,24 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
     }
     SEC(0)
     // ---- histogram over positions (a byte each), then its prefix sums in place ----------------
+    auto* const H64 = lds->template hist64<kHistInPend>();
+    auto* const H32 = lds->template hist32<kHistInPend>();
+    const uint8_t* const H8 = lds->template hist8<kHistInPend>();
     auto clear_histogram = [&]() {
-        lds->P64[lane] = 0ull;
+        H64[lane] = 0ull;
         lds_fence();
     };
     auto histogram = [&](int upto) {
-        if (lane < upto && has_a) { atomicAdd(&lds->P32[qa >> 2], 1u << (8u * (qa & 3u))); }
-        if (lane < upto && has_b) { atomicAdd(&lds->P32[qb >> 2], 1u << (8u * (qb & 3u))); }
+        if (lane < upto && has_a) { atomicAdd(&H32[qa >> 2], 1u << (8u * (qa & 3u))); }
+        if (lane < upto && has_b) { atomicAdd(&H32[qb >> 2], 1u << (8u * (qb & 3u))); }
         lds_fence();
         // lane l owns positions 8l .. 8l+7: byte-wise inclusive sums by one multiply (no byte
         // overflows: a batch holds at most 128 symbols), then the lanes' totals
-        const uint64_t h = lds->P64[lane];
+        const uint64_t h = H64[lane];
         const uint64_t incl = h * 0x0101010101010101ull;
         const uint32_t total = (uint32_t)(incl >> 56);
         const uint32_t base = wave_scan(total) - total;
-        lds->P64[lane] = (incl << 8) + (uint64_t)base * 0x0101010101010101ull;     // exclusive: P[i] = symbols at positions < i
+        H64[lane] = (incl << 8) + (uint64_t)base * 0x0101010101010101ull;     // exclusive: P[i] = symbols at positions < i
         lds_fence();
     };
     clear_histogram();                                   // (does not depend on the cut below: issued before its wait)
@@ -1428,9 +1459,9 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
     uint32_t st[kLitRows], en[kLitRows], pst[kLitRows], pen[kLitRows];
 #pragma unroll
     for (int k = 0; k < kLitRows; k++) { st[k] = r_pos(rf[k]); en[k] = r_pos(rl[k]) + 1u; }
-    const uint32_t p_a0 = lds->P8[qa], p_a1 = lds->P8[qa + 1u], p_b0 = lds->P8[qb], p_b1 = lds->P8[qb + 1u];
+    const uint32_t p_a0 = H8[qa], p_a1 = H8[qa + 1u], p_b0 = H8[qb], p_b1 = H8[qb + 1u];
 #pragma unroll
-    for (int k = 0; k < kLitRows; k++) { pst[k] = lds->P8[st[k]]; pen[k] = lds->P8[en[k]]; }
+    for (int k = 0; k < kLitRows; k++) { pst[k] = H8[st[k]]; pen[k] = H8[en[k]]; }
     // ---- every touched node's test: f + n <= count of its partner (a lo child's sibling, a hi child's
     //      uncle); the tokens' own leaves first (duplicates test the same node twice: harmless) -------------
     // per tested node, kept in a register: its position run and how many chains may still pass it
@@ -1493,7 +1524,7 @@ __device__ __forceinline__ int bump_batch(TreeLds* lds, const uint32_t* code, co
         histogram(ok);
 #pragma unroll
         for (int row = 0; row < kLitRows; row++) {
-            nl[row] = (uint32_t)lds->P8[(sel[row] >> 9) & 0x1FFu] - (uint32_t)lds->P8[sel[row] & 0x1FFu];
+            nl[row] = (uint32_t)H8[(sel[row] >> 9) & 0x1FFu] - (uint32_t)H8[sel[row] & 0x1FFu];
         }
     }
     SEC(3)
