@@ -35,6 +35,7 @@
 #include "sqz_device.h"
 #include "sqz_kernels.h"
 #include "sort_bases.h"
+#include "sort_rank.h"
 
 namespace sqzk {
 
@@ -87,21 +88,10 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) {
     return reinterpret_cast<const U32u*>(p)->v;
 }
 
-// lanes of this wave with the same digit (of `bits` bits) and valid, as a 64-bit mask.  Per bit: the lane's bit spread
-// over a dword (one v_bfe_i32), one ballot, and per half of the mask an xnor and an and.
+// lanes of this wave with the same digit (of `bits` bits) and valid, as a 64-bit mask (sort_rank.h).  Per bit: the
+// lane's bit spread over a dword (one v_bfe_i32), one ballot of its sign, and per half of the mask one v_bitop3_b32.
 __device__ __forceinline__ uint64_t peers_of(uint32_t digit, bool valid, int bits) {
-    const uint64_t all = __ballot(valid);
-    uint32_t lo = (uint32_t)all, hi = (uint32_t)(all >> 32);
-#pragma unroll
-    for (int bit = 0; bit < 10; bit++) {
-        if (bit < bits) {
-            const uint32_t mine = (uint32_t)((int32_t)(digit << (31 - bit)) >> 31);     // all ones: the bit is set
-            const uint64_t m = __ballot(mine != 0u);
-            lo &= ~((uint32_t)m ^ mine);                                                // set ? m : ~m
-            hi &= ~((uint32_t)(m >> 32) ^ mine);
-        }
-    }
-    return ((uint64_t)hi << 32) | lo;
+    return sort_rank_peers(digit, valid, bits, [](bool p) { return (uint64_t)__ballot(p); });
 }
 
 __device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {   // popcount of mask below this lane
