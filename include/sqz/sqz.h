@@ -992,6 +992,71 @@ SQZ_API int sqz_hip_frames_decode(const void* d_frames, const struct sqz_frames_
                                   int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
                                   void* stream);
 
+/* Batches with byte-shuffled (version 4) frames: the calls above with one element size per frame, for a set of tensors
+ * -- many frames of numeric data whose element size differs from one to the next.  The five calls above keep their
+ * behaviour, their refusal of version 4 included; these are opt-in.  Everything said above holds unless said otherwise.
+ *
+ * ENCODE.  elem_bytes: a HOST array of k words, each 0, 2, 4 or 8, brought to the device by a second asynchronous copy
+ * under content_bytes' lifetime rule.  Frame f is byte for byte what the single call writes for that content:
+ * sqz_hip_frame_encode_parse for elem_bytes[f] == 0 (version 1 or 2), sqz_hip_frame_encode_shuf with elem_bytes[f]
+ * otherwise (version 4, flags bit 2 set in the header; `flags` itself is 0 or SQZ_FRAME_STORED as above).  Status and
+ * d_err are the single call's too: a frame whose shuffled bytes the block encoder refuses (E2BIG from the emit
+ * kernel's tree guard) is refused alone.  frame_at[f] = the sum over g < f of sqz_frame_bound_shuf(content_bytes[g],
+ * block_bits, flags | SQZ_FRAME_SHUFFLE) where elem_bytes[g] != 0 and of sqz_frame_bound_ex(..) where it is 0, each
+ * rounded up to 16; sqz_hip_frames_bound_shuf returns frame_at[k], and 0 in addition for a null elem_bytes or a value
+ * that is none of the four.  The contents are shuffled (or, for the frames with 0, copied) into the scratch by ONE
+ * launch, and the block encoder reads them there; checksums and stored blocks are taken from d_in.  The number of
+ * launches does not depend on k.  When every elem_bytes[f] is 0 the call enqueues exactly what sqz_hip_frames_encode
+ * enqueues and needs exactly its scratch.
+ * EINVAL at the call, nothing enqueued: everything sqz_hip_frames_encode refuses; a null elem_bytes; a value that is
+ *   none of 0, 2, 4, 8.  k == 0 returns 0.  ENODEV after the argument checks.
+ * Scratch, when one elem_bytes[f] at least is not 0 (S = total content, T = total blocks, every term rounded up to 256):
+ *       sqz_hip_frames_encode_scratch_bytes_shuf = sqz_hip_frames_encode_scratch_bytes(content_bytes, k, b, flags)
+ *           + 4 k + (4 T + 4) + (S + 16)      [element sizes per frame and per block; the content as the encoder reads it]
+ *   and sqz_hip_frames_encode_scratch_bytes(..) itself when all are 0; 0 for parameters out of range.
+ *
+ * DECODE.  The same sqz_frames_item; for these two calls its last word carries the frame's elem_bytes: 0 for a frame
+ * of version 1 or 2, else what sqz_frame_elem said about a host copy of header, index and record (2, 4 or 8).  Any mix
+ * of versions 1, 2 and 4.  Per frame the checks are sqz_hip_frame_decode_shuf's for a version-4 header and
+ * sqz_hip_frame_decode's for the others, in their order; the record must equal the item's elem_bytes.  A version-1 or
+ * version-2 frame for which the item names an element size, a version-4 frame for which it names none, and a version-3
+ * frame are refused (EINVAL), each alone, as above.  The decoder's output lies in the scratch; ONE launch writes the
+ * blocks that are not stored into d_out, shuffled back by their frame's element size or copied; stored blocks are copied
+ * from the frames and the checksums are taken over d_out.  When every item's element size is 0 the call enqueues what
+ * sqz_hip_frames_decode enqueues and needs its scratch.
+ * EINVAL at the call, nothing enqueued: everything sqz_hip_frames_decode refuses, with "a last word that is none of 0,
+ *   2, 4, 8" in the place of "zero != 0".  E2BIG when an avail is below 32 + 8 n_blocks, or below 32 + 8 n_blocks + 8
+ *   where an element size is named (the record).
+ * Scratch, when one element size at least is not 0 (E, X as above, every term rounded up to 256):
+ *       sqz_hip_frames_decode_scratch_bytes_shuf = sqz_hip_frames_decode_scratch_bytes(the items with 0 as last word, k)
+ *           + (4 E + 4) + (X + 16)            [element size per entry; the span of the outputs as the decoder leaves it]
+ *   and sqz_hip_frames_decode_scratch_bytes(..) itself when all are 0; 0 for a table the call would refuse.
+ *
+ * sqz_hip_shuffle_ranges is the pass on its own, sqz_hip_shuffle_blocks with one element size per range: d_elem[b]
+ * (DEVICE array of n words) = 2, 4 or 8 transforms range b as sqz_hip_shuffle_blocks would with that size, 0 copies it
+ * as it is; any other value, like d_skip[b] != 0 (d_skip may be NULL), leaves the range alone.                       */
+SQZ_API uint64_t sqz_hip_frames_bound_shuf(const uint64_t* content_bytes, const uint32_t* elem_bytes, uint32_t k,
+                                           uint32_t block_bits, uint32_t flags,
+                                           uint64_t* frame_at /* k + 1 entries, may be NULL */);
+SQZ_API uint64_t sqz_hip_frames_encode_scratch_bytes_shuf(const uint64_t* content_bytes, const uint32_t* elem_bytes,
+                                                          uint32_t k, uint32_t block_bits, uint32_t flags);
+SQZ_API int sqz_hip_frames_encode_shuf(const void* d_in, const uint64_t* content_bytes, const uint32_t* elem_bytes,
+                                       uint32_t k, uint32_t win_bits, uint32_t block_bits, uint32_t flags, uint32_t parse,
+                                       void* d_frames, uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status,
+                                       int32_t* d_err, void* d_scratch, uint64_t scratch_bytes, void* stream);
+SQZ_API uint64_t sqz_hip_frames_decode_scratch_bytes_shuf(const struct sqz_frames_item* items, uint32_t k);
+SQZ_API int sqz_hip_frames_decode_shuf(const void* d_frames, const struct sqz_frames_item* items, uint32_t k, void* d_out,
+                                       int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                       void* stream);
+SQZ_API int sqz_hip_shuffle_ranges(const void* d_in, const uint64_t* d_off, const uint32_t* d_elem, uint32_t n,
+                                   int inverse, void* d_out, const uint32_t* d_skip, void* stream);
+/* What sqz_hip_shuffle_ranges replaces, for measuring against it (tools/microbench/frames_shuffle_batch_bench.py): ONE
+ * element size and a mask.  elem_bytes 2, 4 or 8: sqz_hip_shuffle_blocks over the ranges with d_mask[b] == 0, the others
+ * left alone; elem_bytes 0: the ranges with d_mask[b] != 0 copied as they are, the others left alone (the copy of stored
+ * blocks, whose mask says which to take).  A mixed batch is up to three calls of the first kind and one of the second. */
+SQZ_API int sqz_hip_shuffle_blocks_masked(const void* d_in, const uint64_t* d_off, uint32_t n, uint32_t elem_bytes,
+                                          int inverse, void* d_out, const uint32_t* d_mask, void* stream);
+
 /* Live timing of the last kernels enqueued through this library on the
  * calling thread's context, measured with HIP events ON THE LAUNCH STREAM.
  * Enabled with sqz_hip_set_timing(1); values in milliseconds.               */

@@ -225,6 +225,14 @@ PROTOTYPES = {
                                         C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
     "sqz_hip_frames_decode_scratch_bytes": (C.c_uint64, [_vp, C.c_uint32]),
     "sqz_hip_frames_decode": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_frames_bound_shuf": (C.c_uint64, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "sqz_hip_frames_encode_scratch_bytes_shuf": (C.c_uint64, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "sqz_hip_frames_encode_shuf": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_frames_decode_scratch_bytes_shuf": (C.c_uint64, [_vp, C.c_uint32]),
+    "sqz_hip_frames_decode_shuf": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sqz_hip_shuffle_ranges": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp]),
+    "sqz_hip_shuffle_blocks_masked": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_int, _vp, _vp, _vp]),
     "sqz_hip_set_finder": (None, [C.c_int]),
     "sqz_hip_get_finder": (C.c_int, []),
     "sqz_hip_set_timing": (None, [C.c_int]),

@@ -696,7 +696,9 @@ int frame_encode_dev(const uint8_t* d_in, uint64_t content_bytes, uint32_t win_b
 void run_frame_decode(const uint8_t* d_in, const uint64_t* in_off, const uint64_t* out_off, uint32_t n,
                       uint64_t size_hint, uint32_t* tokens, uint32_t* counts, uint8_t* d_out, int32_t* d_err,
                       const uint32_t* skip, const uint32_t* stored, uint32_t* crc, const DictDev& dd, hipStream_t st,
-                      uint32_t n_streams = 0, uint8_t* d_shuf = nullptr, uint32_t elem = 0) {
+                      uint32_t n_streams = 0, uint8_t* d_shuf = nullptr, uint32_t elem = 0,
+                      const uint32_t* elems = nullptr) {
+    // elems: a batch of frames -- one element size per entry in place of elem, 0 for an entry that is only copied
     // d_shuf, elem: version 4 -- the expansion writes the shuffled blocks there (same offsets), the inverse shuffle
     // brings every block that is not stored to d_out; stored blocks, checksums and verification then see d_out as ever
     // n_streams: how many of the n entries can be streams at all, where that is fewer (a gather's pseudo-blocks)
@@ -705,7 +707,11 @@ void run_frame_decode(const uint8_t* d_in, const uint64_t* in_off, const uint64_
                                   decode_waves_for(n_streams != 0 ? n_streams : n), st, skip, dd.len); }
     { SpanGuard g(st, SQZ_HIP_K_LZ_EXPAND);
       sqzk::launch_lz_expand(tokens, counts, d_shuf != nullptr ? d_shuf : d_out, out_off, n, st, skip, dd.bytes, dd.len); }
-    if (d_shuf != nullptr) { sqzk::launch_shuffle_blocks(d_shuf, out_off, n, elem, true, d_out, skip, size_hint, st); }
+    if (d_shuf != nullptr && elems != nullptr) {
+        sqzk::launch_shuffle_ranges(d_shuf, out_off, elems, n, true, d_out, skip, size_hint, st);
+    } else if (d_shuf != nullptr) {
+        sqzk::launch_shuffle_blocks(d_shuf, out_off, n, elem, true, d_out, skip, size_hint, st);
+    }
     if (skip != nullptr) {                                  // a stored block ignores the dictionary
         SpanGuard g(st, SQZ_HIP_K_RANGE_COPY);
         sqzk::launch_range_copy(d_in, in_off, d_out, out_off, out_off, stored, n, false, size_hint, st);
@@ -2790,12 +2796,15 @@ int sqz_hip_frame_append_dict(const void* d_frame, uint64_t avail, uint32_t n_bl
 // or blocks + k does not fit 31 bits
 struct FramesEncShape { uint64_t blocks, content, bound; bool ok; };
 static FramesEncShape frames_enc_shape(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits, uint32_t flags,
-                                       uint64_t* frame_at) {
+                                       uint64_t* frame_at, const uint32_t* elem_bytes = nullptr) {
+    // elem_bytes (null: none): a frame with an element size takes sqz_frame_bound_shuf's room
     FramesEncShape S = {0, 0, 0, false};
     for (uint32_t f = 0; f < k; f++) {
         const uint64_t c = content_bytes[f];
         if (c > (1ull << 62)) { return S; }                     // twice the content and more: the bound would wrap
-        const uint64_t slot = align_up(sqz_frame_bound_ex(c, block_bits, flags), 16);
+        const uint64_t slot = align_up(elem_bytes != nullptr && elem_bytes[f] != 0
+                                           ? sqz_frame_bound_shuf(c, block_bits, flags | (uint32_t)SQZ_FRAME_SHUFFLE)
+                                           : sqz_frame_bound_ex(c, block_bits, flags), 16);
         if (frame_at != NULL) { frame_at[f] = S.bound; }
         if (slot == 0 || S.bound > ~slot || S.content > ~c) { return S; }
         S.bound += slot;
@@ -2810,9 +2819,12 @@ static FramesEncShape frames_enc_shape(const uint64_t* content_bytes, uint32_t k
 
 struct FramesEncScratch {
     uint64_t content, in_at, frame_at, base, in_off, slab_off, crc, out_bytes, copy_bytes, dense_rel, dense_off, stored,
-             slabs, codec, codec_bytes, total;
+             slabs, codec, codec_bytes, elem, blk_elem, shuf, total;
 };
-static FramesEncScratch frames_enc_scratch(uint64_t k, uint64_t n, uint64_t content_bytes, uint64_t slab_bytes, bool store) {
+// shuf: a batch with shuffled frames keeps, behind everything else, the k element sizes, one per block of the batch, and
+// the whole content as the encoder reads it
+static FramesEncScratch frames_enc_scratch(uint64_t k, uint64_t n, uint64_t content_bytes, uint64_t slab_bytes, bool store,
+                                           bool shuf = false) {
     FramesEncScratch L = {};
     uint64_t at = 0;
     auto take = [&at](uint64_t bytes) { const uint64_t r = at; at += align_up(bytes, 256); return r; };
@@ -2831,6 +2843,11 @@ static FramesEncScratch frames_enc_scratch(uint64_t k, uint64_t n, uint64_t cont
     L.slabs = take(n * slab_bytes);
     L.codec_bytes = sqz_hip_encode_scratch_bytes((uint32_t)n, content_bytes);
     L.codec = take(L.codec_bytes);
+    if (shuf) {
+        L.elem = take(k * 4);
+        L.blk_elem = take(n * 4 + 4);
+        L.shuf = take(content_bytes + 16);
+    }
     L.total = at;
     return L;
 }
@@ -2852,20 +2869,22 @@ uint64_t sqz_hip_frames_encode_scratch_bytes(const uint64_t* content_bytes, uint
     return frames_enc_scratch(k, S.blocks, S.content, sqz_bound(1ull << block_bits), (flags & SQZ_FRAME_STORED) != 0).total;
 }
 
-int sqz_hip_frames_encode(const void* d_in, const uint64_t* content_bytes, uint32_t k, uint32_t win_bits,
-                          uint32_t block_bits, uint32_t flags, uint32_t parse, void* d_frames, uint64_t capacity,
-                          uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err, void* d_scratch,
-                          uint64_t scratch_bytes, void* stream) {
+// elem_bytes: null for the call there always was; else k element sizes, one of them not 0 (sqz_hip_frames_encode_shuf)
+static int frames_encode_call(const void* d_in, const uint64_t* content_bytes, const uint32_t* elem_bytes, uint32_t k,
+                              uint32_t win_bits, uint32_t block_bits, uint32_t flags, uint32_t parse, void* d_frames,
+                              uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err,
+                              void* d_scratch, uint64_t scratch_bytes, void* stream) {
     if (!parse_ok(parse) || !frame_flags_ok(flags) || !frame_params_ok(win_bits, block_bits)) { return EINVAL; }
     if (k == 0) { return 0; }
     if (content_bytes == NULL || d_frames == NULL || ((uintptr_t)d_frames & 15u) != 0 || d_frame_bytes == NULL ||
         d_status == NULL || d_scratch == NULL || ((uintptr_t)d_scratch & 15u) != 0) { return EINVAL; }
-    const FramesEncShape S = frames_enc_shape(content_bytes, k, block_bits, flags, NULL);
+    const bool shuf = elem_bytes != nullptr;
+    const FramesEncShape S = frames_enc_shape(content_bytes, k, block_bits, flags, NULL, elem_bytes);
     if (!S.ok || (d_in == NULL && S.content > 0) || (d_err == NULL && S.blocks > 0) || capacity < S.bound) { return EINVAL; }
     const uint64_t bb = 1ull << block_bits, slab = sqz_bound(bb);
     const bool store = (flags & SQZ_FRAME_STORED) != 0;
     const uint32_t n = (uint32_t)S.blocks;
-    const FramesEncScratch L = frames_enc_scratch(k, n, S.content, slab, store);
+    const FramesEncScratch L = frames_enc_scratch(k, n, S.content, slab, store, shuf);
     if (scratch_bytes < L.total) { return EINVAL; }
     const int e = device_ready();
     if (e != 0) { return e; }
@@ -2883,9 +2902,17 @@ int sqz_hip_frames_encode(const void* d_in, const uint64_t* content_bytes, uint3
     uint64_t* dense_rel = (uint64_t*)(scratch + L.dense_rel);
     uint64_t* dense_off = (uint64_t*)(scratch + L.dense_off);
     uint32_t* stored = store ? (uint32_t*)(scratch + L.stored) : nullptr;
+    uint32_t* elem = shuf ? (uint32_t*)(scratch + L.elem) : nullptr;
+    uint32_t* blk_elem = shuf ? (uint32_t*)(scratch + L.blk_elem) : nullptr;
     HIP_TRY(hipMemcpyAsync(sizes, content_bytes, (size_t)k * 8, hipMemcpyHostToDevice, st));
-    sqzk::launch_frames_encode_scan(sizes, k, block_bits, flags, in_at, frame_at, base, st);
-    sqzk::launch_frames_plan(sizes, in_at, base, k, block_bits, slab, in_off, slab_off, st);
+    if (shuf) {
+        HIP_TRY(hipMemcpyAsync(elem, elem_bytes, (size_t)k * 4, hipMemcpyHostToDevice, st));
+        sqzk::launch_frames_encode_scan_v4(sizes, elem, k, block_bits, flags, in_at, frame_at, base, st);
+        sqzk::launch_frames_plan_v4(sizes, elem, in_at, base, k, block_bits, slab, in_off, slab_off, blk_elem, st);
+    } else {
+        sqzk::launch_frames_encode_scan(sizes, k, block_bits, flags, in_at, frame_at, base, st);
+        sqzk::launch_frames_plan(sizes, in_at, base, k, block_bits, slab, in_off, slab_off, st);
+    }
     if (n > 0) {
         { SpanGuard g(st, SQZ_HIP_K_CRC32);
           sqzk::launch_crc32_blocks((const uint8_t*)d_in, in_off, n, crc, bb, st); }
@@ -2893,12 +2920,25 @@ int sqz_hip_frames_encode(const void* d_in, const uint64_t* content_bytes, uint3
         const uint64_t slots = (L.codec_bytes - head) / 8;
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + head);
-        run_encode(finder_for(parse), (const uint8_t*)d_in, in_off, n, 1u << win_bits, tokens, counts, tokens,
+        const uint8_t* enc_in = (const uint8_t*)d_in;       // shuffled frames: the encoder reads the whole batch from the
+        if (shuf) {                                         // scratch, every block shuffled by its frame's element size or
+            sqzk::launch_shuffle_ranges((const uint8_t*)d_in, in_off, blk_elem, n, false, scratch + L.shuf, nullptr, bb,
+                                        st);                // copied; checksums (above) and stored blocks (below) keep to
+            enc_in = scratch + L.shuf;                      // the caller's bytes
+        }
+        run_encode(finder_for(parse), enc_in, in_off, n, 1u << win_bits, tokens, counts, tokens,
                    tokens + slots, bb, scratch + L.slabs, slab_off, out_bytes, d_err, 0, 0, slots, nullptr, st, parse);
     }
     { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
-      sqzk::launch_frames_index(out_bytes, d_err, crc, sizes, frame_at, base, k, win_bits, block_bits, flags,
-                                (uint8_t*)d_frames, copy_bytes, dense_rel, dense_off, stored, d_frame_bytes, d_status, st); }
+      if (shuf) {
+          sqzk::launch_frames_index_v4(out_bytes, d_err, crc, sizes, elem, frame_at, base, k, win_bits, block_bits, flags,
+                                       (uint8_t*)d_frames, copy_bytes, dense_rel, dense_off, stored, d_frame_bytes,
+                                       d_status, st);
+      } else {
+          sqzk::launch_frames_index(out_bytes, d_err, crc, sizes, frame_at, base, k, win_bits, block_bits, flags,
+                                    (uint8_t*)d_frames, copy_bytes, dense_rel, dense_off, stored, d_frame_bytes, d_status,
+                                    st);
+      } }
     if (n > 0) {
         sqzk::launch_compact_blocks(scratch + L.slabs, slab_off, copy_bytes, n, (uint8_t*)d_frames, dense_off, bb / 2, st);
         if (store) {                                        // the stored blocks' content, where the indexes say
@@ -2910,14 +2950,74 @@ int sqz_hip_frames_encode(const void* d_in, const uint64_t* content_bytes, uint3
     return hip_errno(hipGetLastError());
 }
 
+int sqz_hip_frames_encode(const void* d_in, const uint64_t* content_bytes, uint32_t k, uint32_t win_bits,
+                          uint32_t block_bits, uint32_t flags, uint32_t parse, void* d_frames, uint64_t capacity,
+                          uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err, void* d_scratch,
+                          uint64_t scratch_bytes, void* stream) {
+    return frames_encode_call(d_in, content_bytes, nullptr, k, win_bits, block_bits, flags, parse, d_frames, capacity,
+                              d_frame_bytes, d_status, d_err, d_scratch, scratch_bytes, stream);
+}
+
+// ---- batches that know version 4: one element size per frame, 0 for a frame that is not shuffled
+// 0: every one of the k values is 0 (the calls there always were do the work); 1: one at least is 2, 4 or 8;
+// -1: a value that is none of these, or no array
+static int frames_elem_kind(const uint32_t* elem_bytes, uint32_t k) {
+    if (elem_bytes == NULL) { return k == 0 ? 0 : -1; }
+    int kind = 0;
+    for (uint32_t f = 0; f < k; f++) {
+        if (elem_bytes[f] != 0) {
+            if (!elem_ok(elem_bytes[f])) { return -1; }
+            kind = 1;
+        }
+    }
+    return kind;
+}
+
+uint64_t sqz_hip_frames_bound_shuf(const uint64_t* content_bytes, const uint32_t* elem_bytes, uint32_t k,
+                                   uint32_t block_bits, uint32_t flags, uint64_t* frame_at) {
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        !frame_flags_ok(flags) || (content_bytes == NULL && k > 0) || frames_elem_kind(elem_bytes, k) < 0) { return 0; }
+    const FramesEncShape S = frames_enc_shape(content_bytes, k, block_bits, flags, frame_at, elem_bytes);
+    return S.ok ? S.bound : 0;
+}
+
+uint64_t sqz_hip_frames_encode_scratch_bytes_shuf(const uint64_t* content_bytes, const uint32_t* elem_bytes, uint32_t k,
+                                                  uint32_t block_bits, uint32_t flags) {
+    const int kind = frames_elem_kind(elem_bytes, k);
+    if (kind < 0) { return 0; }
+    if (kind == 0) { return sqz_hip_frames_encode_scratch_bytes(content_bytes, k, block_bits, flags); }
+    if (block_bits < (uint32_t)sqz_frame_min_block_bits || block_bits > (uint32_t)sqz_frame_max_block_bits ||
+        !frame_flags_ok(flags) || content_bytes == NULL) { return 0; }
+    const FramesEncShape S = frames_enc_shape(content_bytes, k, block_bits, flags, NULL, elem_bytes);
+    if (!S.ok) { return 0; }
+    return frames_enc_scratch(k, S.blocks, S.content, sqz_bound(1ull << block_bits), (flags & SQZ_FRAME_STORED) != 0,
+                              true).total;
+}
+
+int sqz_hip_frames_encode_shuf(const void* d_in, const uint64_t* content_bytes, const uint32_t* elem_bytes, uint32_t k,
+                               uint32_t win_bits, uint32_t block_bits, uint32_t flags, uint32_t parse, void* d_frames,
+                               uint64_t capacity, uint64_t* d_frame_bytes, int32_t* d_status, int32_t* d_err,
+                               void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    if (!parse_ok(parse) || !frame_flags_ok(flags) || !frame_params_ok(win_bits, block_bits)) { return EINVAL; }
+    if (k == 0) { return 0; }
+    const int kind = frames_elem_kind(elem_bytes, k);
+    if (kind < 0) { return EINVAL; }
+    // no frame is shuffled: exactly what sqz_hip_frames_encode enqueues, no pass and no scratch for one
+    return frames_encode_call(d_in, content_bytes, kind == 0 ? nullptr : elem_bytes, k, win_bits, block_bits, flags,
+                              parse, d_frames, capacity, d_frame_bytes, d_status, d_err, d_scratch, scratch_bytes, stream);
+}
+
 // what the host works out from the table of a decode: total blocks, the span of the outputs, the largest block's size
 // as far as the table says (it only sizes launches); err: EINVAL / E2BIG as the call answers them
-struct FramesDecShape { uint64_t blocks, extent, hint; int err; };
-static FramesDecShape frames_dec_shape(const struct sqz_frames_item* items, uint32_t k) {
-    FramesDecShape S = {0, 0, 1, 0};
+// shuf (the _shuf calls): the last word of an item is the frame's element size, 0, 2, 4 or 8, and any: one is not 0
+struct FramesDecShape { uint64_t blocks, extent, hint; int err; bool any; };
+static FramesDecShape frames_dec_shape(const struct sqz_frames_item* items, uint32_t k, bool shuf = false) {
+    FramesDecShape S = {0, 0, 1, 0, false};
     for (uint32_t f = 0; f < k; f++) {
         const struct sqz_frames_item& it = items[f];
-        if ((it.frame_at & 15u) != 0 || it.zero != 0 || it.avail > ~it.frame_at || it.content_bytes > ~it.out_at) {
+        if (it.zero != 0) { S.any = true; }
+        if ((it.frame_at & 15u) != 0 || (shuf ? it.zero != 0 && !elem_ok(it.zero) : it.zero != 0) ||
+            it.avail > ~it.frame_at || it.content_bytes > ~it.out_at) {
             S.err = EINVAL;
             return S;
         }
@@ -2933,13 +3033,17 @@ static FramesDecShape frames_dec_shape(const struct sqz_frames_item* items, uint
     if (k > 0) { S.extent = items[k - 1].out_at + items[k - 1].content_bytes - items[0].out_at; }
     if (S.extent > (1ull << 60)) { S.err = EINVAL; return S; }     // four bytes of scratch per byte of it
     for (uint32_t f = 0; f < k; f++) {
-        if (items[f].avail < 32 + 8 * (uint64_t)items[f].n_blocks) { S.err = E2BIG; return S; }
+        if (items[f].avail < 32 + 8 * (uint64_t)items[f].n_blocks + (items[f].zero != 0 ? 8 : 0)) { S.err = E2BIG; return S; }
     }
     return S;
 }
 
-struct FramesDecScratch { uint64_t items, base, in_off, out_off, skip, stored, crc, err, codec, codec_bytes, total; };
-static FramesDecScratch frames_dec_scratch(uint64_t k, uint64_t entries, uint64_t extent) {
+struct FramesDecScratch {
+    uint64_t items, base, in_off, out_off, skip, stored, crc, err, codec, codec_bytes, ent_elem, shuf, total;
+};
+// shuf: a batch with shuffled frames keeps, behind everything else, one element size per entry and the span of the
+// outputs once more, as the decoder leaves it
+static FramesDecScratch frames_dec_scratch(uint64_t k, uint64_t entries, uint64_t extent, bool shuf = false) {
     FramesDecScratch L = {};
     uint64_t at = 0;
     auto take = [&at](uint64_t bytes) { const uint64_t r = at; at += align_up(bytes, 256); return r; };
@@ -2953,6 +3057,10 @@ static FramesDecScratch frames_dec_scratch(uint64_t k, uint64_t entries, uint64_
     L.err = take(entries * 4 + 4);
     L.codec_bytes = sqz_hip_decode_scratch_bytes((uint32_t)entries, extent);
     L.codec = take(L.codec_bytes);
+    if (shuf) {
+        L.ent_elem = take(entries * 4 + 4);
+        L.shuf = take(extent + 16);
+    }
     L.total = at;
     return L;
 }
@@ -2964,15 +3072,18 @@ uint64_t sqz_hip_frames_decode_scratch_bytes(const struct sqz_frames_item* items
     return S.err != 0 ? 0 : frames_dec_scratch(k, S.blocks + k, S.extent).total;
 }
 
-int sqz_hip_frames_decode(const void* d_frames, const struct sqz_frames_item* items, uint32_t k, void* d_out,
-                          int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+// with_elem: sqz_hip_frames_decode_shuf, where an item's last word is the frame's element size
+static int frames_decode_call(const void* d_frames, const struct sqz_frames_item* items, uint32_t k, void* d_out,
+                              int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream,
+                              bool with_elem) {
     if (k == 0) { return 0; }
     if (items == NULL || d_frames == NULL || ((uintptr_t)d_frames & 15u) != 0 || d_status == NULL || d_scratch == NULL ||
         ((uintptr_t)d_scratch & 15u) != 0) { return EINVAL; }
-    const FramesDecShape S = frames_dec_shape(items, k);
+    const FramesDecShape S = frames_dec_shape(items, k, with_elem);
     if (S.err == EINVAL || (S.blocks > 0 && (d_out == NULL || d_err == NULL))) { return EINVAL; }
     const uint32_t n = (uint32_t)S.blocks, entries = n + k;
-    const FramesDecScratch L = frames_dec_scratch(k, entries, S.extent);
+    const bool shuf = with_elem && S.any;                   // no element size named: what there always was
+    const FramesDecScratch L = frames_dec_scratch(k, entries, S.extent, shuf);
     if (scratch_bytes < L.total) { return EINVAL; }
     if (S.err != 0) { return S.err; }
     const int e = device_ready();
@@ -2990,15 +3101,69 @@ int sqz_hip_frames_decode(const void* d_frames, const struct sqz_frames_item* it
     const uint64_t out_base = items[0].out_at;
     HIP_TRY(hipMemcpyAsync(table, items, (size_t)k * sizeof(struct sqz_frames_item), hipMemcpyHostToDevice, st));
     sqzk::launch_frames_decode_scan(table, k, base, st);
+    uint32_t* ent_elem = shuf ? (uint32_t*)(scratch + L.ent_elem) : nullptr;
     { SpanGuard g(st, SQZ_HIP_K_FRAME_INDEX);
-      sqzk::launch_frames_open((const uint8_t*)d_frames, table, base, k, out_base, in_off, out_off, skip, stored,
-                               d_status, st); }
+      if (shuf) {
+          sqzk::launch_frames_open_v4((const uint8_t*)d_frames, table, base, k, out_base, in_off, out_off, skip, stored,
+                                      ent_elem, d_status, st);
+      } else {
+          sqzk::launch_frames_open((const uint8_t*)d_frames, table, base, k, out_base, in_off, out_off, skip, stored,
+                                   d_status, st);
+      } }
     if (n > 0) {
         uint32_t* counts = (uint32_t*)(scratch + L.codec);
         uint32_t* tokens = (uint32_t*)(scratch + L.codec + align_up((uint64_t)entries * 4, 256));
+        // shuffled frames: the expansion writes the whole span into the scratch, the inverse pass brings every block
+        // that is not stored to d_out, shuffled back by its frame's element size or copied
         run_frame_decode((const uint8_t*)d_frames, in_off, out_off, entries, S.hint, tokens, counts,
-                         (uint8_t*)d_out + out_base, err, skip, stored, crc, DictDev(), st, n);
+                         (uint8_t*)d_out + out_base, err, skip, stored, crc, DictDev(), st, n,
+                         shuf ? scratch + L.shuf : nullptr, 0, ent_elem);
         sqzk::launch_frames_verify((const uint8_t*)d_frames, table, base, k, crc, d_status, err, d_err, st);
+    }
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_frames_decode(const void* d_frames, const struct sqz_frames_item* items, uint32_t k, void* d_out,
+                          int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return frames_decode_call(d_frames, items, k, d_out, d_err, d_status, d_scratch, scratch_bytes, stream, false);
+}
+
+uint64_t sqz_hip_frames_decode_scratch_bytes_shuf(const struct sqz_frames_item* items, uint32_t k) {
+    if (items == NULL && k > 0) { return 0; }
+    const FramesDecShape S = frames_dec_shape(items, k, true);
+    return S.err != 0 ? 0 : frames_dec_scratch(k, S.blocks + k, S.extent, S.any).total;
+}
+
+int sqz_hip_frames_decode_shuf(const void* d_frames, const struct sqz_frames_item* items, uint32_t k, void* d_out,
+                               int32_t* d_err, int32_t* d_status, void* d_scratch, uint64_t scratch_bytes,
+                               void* stream) {
+    return frames_decode_call(d_frames, items, k, d_out, d_err, d_status, d_scratch, scratch_bytes, stream, true);
+}
+
+int sqz_hip_shuffle_ranges(const void* d_in, const uint64_t* d_off, const uint32_t* d_elem, uint32_t n, int inverse,
+                           void* d_out, const uint32_t* d_skip, void* stream) {
+    if (n == 0) { return 0; }
+    if (d_in == NULL || d_off == NULL || d_elem == NULL || d_out == NULL || d_in == d_out) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    sqzk::launch_shuffle_ranges((const uint8_t*)d_in, d_off, d_elem, n, inverse != 0, (uint8_t*)d_out, d_skip, 0,
+                                (hipStream_t)stream);
+    return hip_errno(hipGetLastError());
+}
+
+int sqz_hip_shuffle_blocks_masked(const void* d_in, const uint64_t* d_off, uint32_t n, uint32_t elem_bytes, int inverse,
+                                  void* d_out, const uint32_t* d_mask, void* stream) {
+    if (elem_bytes != 0 && !elem_ok(elem_bytes)) { return EINVAL; }
+    if (n == 0) { return 0; }
+    if (d_in == NULL || d_off == NULL || d_out == NULL || d_mask == NULL || d_in == d_out) { return EINVAL; }
+    const int e = device_ready();
+    if (e != 0) { return e; }
+    if (elem_bytes == 0) {
+        sqzk::launch_range_copy((const uint8_t*)d_in, d_off, (uint8_t*)d_out, d_off, d_off, d_mask, n, false, 0,
+                                (hipStream_t)stream);
+    } else {
+        sqzk::launch_shuffle_blocks((const uint8_t*)d_in, d_off, n, elem_bytes, inverse != 0, (uint8_t*)d_out, d_mask, 0,
+                                    (hipStream_t)stream);
     }
     return hip_errno(hipGetLastError());
 }

@@ -2125,6 +2125,214 @@ void frames_verify_kernel(const uint8_t* __restrict__ frames, const sqz_frames_i
     }
 }
 
+// ---- the flavours that know version 4: elem[f] = frame f's element size (2, 4 or 8), 0 an unshuffled frame.  Siblings
+// of the kernels above, which stay as they are; what a frame's workgroup does is the same body either way.
+
+// sqz_frame_bound_shuf where the frame is shuffled (the record's 8 bytes in front of the padding), sqz_frame_bound_ex
+// where it is not, rounded up to 16
+__device__ __forceinline__ uint64_t frames_slot_bytes_v4(uint64_t content_bytes, uint32_t block_bits, bool store,
+                                                         uint32_t elem_bytes) {
+    const uint64_t bb = 1ull << block_bits, full = content_bytes >> block_bits, tail = content_bytes & (bb - 1);
+    const uint64_t n = full + (tail != 0 ? 1 : 0);
+    const uint64_t payload_off = (32 + 8 * n + (elem_bytes != 0 ? 8 : 0) + 15) & ~(uint64_t)15;
+    const uint64_t payload = store ? (content_bytes + 7) & ~(uint64_t)7
+                                   : full * ((2 * bb + 1024 + 7) & ~(uint64_t)7) +
+                                     (tail != 0 ? (2 * tail + 1024 + 7) & ~(uint64_t)7 : 0);
+    return (payload_off + payload + 15) & ~(uint64_t)15;
+}
+
+// encode_scan over those bounds
+__global__ __launch_bounds__(kFramesThreads)
+void frames_encode_scan_v4_kernel(const uint64_t* __restrict__ content_bytes, const uint32_t* __restrict__ elem,
+                                  uint32_t k, uint32_t block_bits, uint32_t flags, uint64_t* __restrict__ in_at,
+                                  uint64_t* __restrict__ frame_at, uint32_t* __restrict__ base) {
+    __shared__ uint64_t shares[3][kFramesThreads];
+    const uint32_t t = threadIdx.x;
+    const bool store = (flags & kFrameStored) != 0;
+    const uint64_t per = ((uint64_t)k + kFramesThreads - 1) / kFramesThreads;
+    const uint64_t f0 = t * per < k ? t * per : k;
+    const uint64_t f1 = f0 + per < k ? f0 + per : k;
+    const uint64_t bb = 1ull << block_bits;
+    uint64_t at[3] = {0, 0, 0};
+    for (uint64_t f = f0; f < f1; f++) {
+        const uint64_t c = content_bytes[f];
+        at[0] += c;
+        at[1] += frames_slot_bytes_v4(c, block_bits, store, elem[f]);
+        at[2] += (c >> block_bits) + ((c & (bb - 1)) != 0 ? 1 : 0);
+    }
+    frames_scan_shares(at, shares);
+    for (uint64_t f = f0; f < f1; f++) {
+        const uint64_t c = content_bytes[f];
+        in_at[f] = at[0]; frame_at[f] = at[1]; base[f] = (uint32_t)at[2];
+        at[0] += c;
+        at[1] += frames_slot_bytes_v4(c, block_bits, store, elem[f]);
+        at[2] += (c >> block_bits) + ((c & (bb - 1)) != 0 ? 1 : 0);
+    }
+    if (f1 == k && (f0 < f1 || t == 0)) { in_at[k] = at[0]; frame_at[k] = at[1]; base[k] = (uint32_t)at[2]; }
+}
+
+// plan, and the element size of every block of the batch for shuffle_ranges_kernel
+__global__ __launch_bounds__(kFramesThreads)
+void frames_plan_v4_kernel(const uint64_t* __restrict__ content_bytes, const uint32_t* __restrict__ elem,
+                           const uint64_t* __restrict__ in_at, const uint32_t* __restrict__ base, uint32_t k,
+                           uint32_t block_bits, uint64_t slab_bytes, uint64_t* __restrict__ in_off,
+                           uint64_t* __restrict__ slab_off, uint32_t* __restrict__ blk_elem) {
+    const uint32_t f = blockIdx.x;
+    if (f >= k) { return; }
+    const uint64_t g0 = base[f], n = base[f + 1] - base[f], at = in_at[f], c = content_bytes[f];
+    const uint32_t e = elem[f];
+    for (uint64_t b = threadIdx.x; b < n; b += kFramesThreads) {
+        in_off[g0 + b] = at + (b << block_bits);   // b < n: inside the content
+        slab_off[g0 + b] = (g0 + b) * slab_bytes;
+        blk_elem[g0 + b] = e;
+    }
+    if (f == k - 1 && threadIdx.x == 0) { in_off[g0 + n] = at + c; slab_off[g0 + n] = (g0 + n) * slab_bytes; }
+}
+
+// index: frame_index_body<false, kShuf> by elem[f]; a shuffled frame's checksum takes the record in, which is one more
+// 8-byte entry behind the last lane's share
+__global__ __launch_bounds__(kFramesThreads)
+void frames_index_v4_kernel(const uint64_t* __restrict__ out_bytes, const int32_t* __restrict__ err,
+                            const uint32_t* __restrict__ crc, const uint64_t* __restrict__ content_bytes,
+                            const uint32_t* __restrict__ elem, const uint64_t* __restrict__ frame_at,
+                            const uint32_t* __restrict__ base, uint32_t k, uint32_t win_bits, uint32_t block_bits,
+                            uint32_t flags, uint8_t* __restrict__ frames, uint64_t* __restrict__ copy_bytes,
+                            uint64_t* __restrict__ dense_rel, uint64_t* __restrict__ dense_off,
+                            uint32_t* __restrict__ stored, uint64_t* __restrict__ frame_bytes_out,
+                            int32_t* __restrict__ status_out) {
+    __shared__ uint64_t idx_range[2];
+    const uint32_t f = blockIdx.x;
+    if (f >= k) { return; }
+    const uint32_t t = threadIdx.x;
+    const uint64_t g0 = base[f];
+    const uint32_t n = base[f + 1] - base[f];
+    const uint64_t at = frame_at[f], capacity = frame_at[f + 1] - at, content = content_bytes[f];
+    const uint32_t e = elem[f];                    // the same for the whole workgroup
+    uint8_t* const frame = frames + at;
+    uint64_t* const rel = dense_rel + g0 + f;
+    uint32_t* const mask = (flags & kFrameStored) != 0 ? stored + g0 : nullptr;
+    if (e != 0) {
+        frame_index_body<false, true>(out_bytes + g0, err + g0, crc + g0, n, content, win_bits, block_bits, frame,
+                                      capacity, copy_bytes + g0, rel, idx_range, frame_bytes_out + f, status_out + f,
+                                      (flags & kFrameStored) | kFrameShuffle, mask, e, nullptr);
+    } else {
+        frame_index_body<false>(out_bytes + g0, err + g0, crc + g0, n, content, win_bits, block_bits, frame, capacity,
+                                copy_bytes + g0, rel, idx_range, frame_bytes_out + f, status_out + f,
+                                flags & kFrameStored, mask, 0u, nullptr);
+    }
+    __syncthreads();                               // the body's writes, lane 0's status among them
+    const bool ok = status_out[f] == 0;
+    const uint64_t per = ((uint64_t)n + 255) / 256;
+    const uint64_t b0 = t * per < n ? t * per : n;
+    const uint64_t b1 = b0 + per < n ? b0 + per : n;
+    const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
+    uint32_t r = 0;
+    uint64_t count = b1 - b0;
+    for (uint64_t b = b0; b < b1; b++) {
+        dense_off[g0 + b] = ok ? at + rel[b] : 0;
+        if (ok) { r = crc_word(crc_word(r ^ index[2 * b]) ^ index[2 * b + 1]); }
+    }
+    if (e != 0 && t == kFramesThreads - 1) {       // the last share, empty or not, ends where the record begins
+        if (ok) { r = crc_word(crc_word(r ^ index[2 * (uint64_t)n]) ^ index[2 * (uint64_t)n + 1]); }
+        count += 1;
+    }
+    uint32_t power;
+    const uint32_t idx_crc = index_crc_workgroup(r, count, &power);
+    if (ok && t == 0) { reinterpret_cast<uint32_t*>(frame)[7] = gf_mul(crc32_small(frame, 28), power) ^ idx_crc; }
+    if (f == k - 1 && t == 0) { dense_off[g0 + n] = ok ? at + rel[n] : 0; }
+}
+
+// open: items[f].zero is the caller's element size for frame f.  A version-4 header with one named: frame_open_body's
+// version-4 reader with it; a version-4 header with none, or another version with one: EINVAL, nothing of the frame
+// behind its header is read; else the reader of versions 1 and 2 as in frames_open_kernel.  ent_elem: the element size
+// of every entry for shuffle_ranges_kernel, 0 for the switched-off entry of every frame.
+__global__ __launch_bounds__(kFramesThreads)
+void frames_open_v4_kernel(const uint8_t* __restrict__ frames, const sqz_frames_item* __restrict__ items,
+                           const uint32_t* __restrict__ base, uint32_t k, uint64_t out_base,
+                           uint64_t* __restrict__ in_off, uint64_t* __restrict__ out_off, uint32_t* __restrict__ skip,
+                           uint32_t* __restrict__ stored, uint32_t* __restrict__ ent_elem,
+                           int32_t* __restrict__ status_out) {
+    __shared__ uint32_t idx_crc;
+    const uint32_t f = blockIdx.x;
+    if (f >= k) { return; }
+    const uint32_t t = threadIdx.x;
+    const uint64_t at = items[f].frame_at, avail = items[f].avail, content = items[f].content_bytes;
+    const uint64_t to = items[f].out_at - out_base;
+    const uint32_t n = items[f].n_blocks, e = items[f].zero;
+    const uint64_t e0 = (uint64_t)base[f] + f;
+    const uint8_t* const frame = frames + at;
+    const bool v4 = frame[4] == 4;                 // the same for the whole workgroup, like e
+    if (v4 != (e != 0)) {
+        if (t == 0) { status_out[f] = kErrEINVAL; }
+    } else {
+        const uint32_t* const index = reinterpret_cast<const uint32_t*>(frame + 32);
+        const uint64_t per = ((uint64_t)n + 255) / 256;
+        const uint64_t b0 = t * per < n ? t * per : n;
+        const uint64_t b1 = b0 + per < n ? b0 + per : n;
+        uint32_t r = 0;
+        uint64_t count = b1 - b0;
+        for (uint64_t b = b0; b < b1; b++) { r = crc_word(crc_word(r ^ index[2 * b]) ^ index[2 * b + 1]); }
+        if (v4 && t == kFramesThreads - 1) {       // the record, behind the last share
+            r = crc_word(crc_word(r ^ index[2 * (uint64_t)n]) ^ index[2 * (uint64_t)n + 1]);
+            count += 1;
+        }
+        uint32_t power;
+        const uint32_t c = index_crc_workgroup(r, count, &power);
+        if (t == 0) { idx_crc = c; }
+        __syncthreads();
+        if (v4) {
+            frame_open_body<false, false, true>(frame, avail, n, content, 0u, n, &idx_crc, in_off + e0, out_off + e0,
+                                                status_out + f, stored + e0, e, nullptr, 0u);
+        } else {
+            frame_open_body<false>(frame, avail, n, content, 0u, n, &idx_crc, in_off + e0, out_off + e0, status_out + f,
+                                   stored + e0, 0u, nullptr, 0u);
+        }
+    }
+    __syncthreads();
+    const bool ok = status_out[f] == 0;
+    for (uint64_t j = t; j <= n; j += kFramesThreads) {
+        in_off[e0 + j] = ok ? at + in_off[e0 + j] : at;
+        out_off[e0 + j] = ok ? to + out_off[e0 + j] : to;
+        const uint32_t raw = ok && j < n ? stored[e0 + j] : 0u;
+        stored[e0 + j] = raw;
+        skip[e0 + j] = ok && j < n ? raw : 1u;
+        ent_elem[e0 + j] = j < n ? e : 0u;
+    }
+    __syncthreads();
+    if (f == k - 1 && t == 0) { in_off[e0 + n + 1] = in_off[e0 + n]; out_off[e0 + n + 1] = out_off[e0 + n]; }
+}
+
+void launch_frames_encode_scan_v4(const uint64_t* content_bytes, const uint32_t* elem, uint32_t k, uint32_t block_bits,
+                                  uint32_t flags, uint64_t* in_at, uint64_t* frame_at, uint32_t* base,
+                                  hipStream_t stream) {
+    hipLaunchKernelGGL(frames_encode_scan_v4_kernel, dim3(1), dim3(kFramesThreads), 0, stream, content_bytes, elem, k,
+                       block_bits, flags, in_at, frame_at, base);
+}
+
+void launch_frames_plan_v4(const uint64_t* content_bytes, const uint32_t* elem, const uint64_t* in_at,
+                           const uint32_t* base, uint32_t k, uint32_t block_bits, uint64_t slab_bytes, uint64_t* in_off,
+                           uint64_t* slab_off, uint32_t* blk_elem, hipStream_t stream) {
+    hipLaunchKernelGGL(frames_plan_v4_kernel, dim3(k), dim3(kFramesThreads), 0, stream, content_bytes, elem, in_at, base,
+                       k, block_bits, slab_bytes, in_off, slab_off, blk_elem);
+}
+
+void launch_frames_index_v4(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc,
+                            const uint64_t* content_bytes, const uint32_t* elem, const uint64_t* frame_at,
+                            const uint32_t* base, uint32_t k, uint32_t win_bits, uint32_t block_bits, uint32_t flags,
+                            uint8_t* frames, uint64_t* copy_bytes, uint64_t* dense_rel, uint64_t* dense_off,
+                            uint32_t* stored, uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frames_index_v4_kernel, dim3(k), dim3(kFramesThreads), 0, stream, out_bytes, err, crc,
+                       content_bytes, elem, frame_at, base, k, win_bits, block_bits, flags, frames, copy_bytes,
+                       dense_rel, dense_off, stored, frame_bytes_out, status_out);
+}
+
+void launch_frames_open_v4(const uint8_t* frames, const sqz_frames_item* items, const uint32_t* base, uint32_t k,
+                           uint64_t out_base, uint64_t* in_off, uint64_t* out_off, uint32_t* skip, uint32_t* stored,
+                           uint32_t* ent_elem, int32_t* status_out, hipStream_t stream) {
+    hipLaunchKernelGGL(frames_open_v4_kernel, dim3(k), dim3(kFramesThreads), 0, stream, frames, items, base, k,
+                       out_base, in_off, out_off, skip, stored, ent_elem, status_out);
+}
+
 void launch_frames_encode_scan(const uint64_t* content_bytes, uint32_t k, uint32_t block_bits, uint32_t flags,
                                uint64_t* in_at, uint64_t* frame_at, uint32_t* base, hipStream_t stream) {
     hipLaunchKernelGGL(frames_encode_scan_kernel, dim3(1), dim3(kFramesThreads), 0, stream, content_bytes, k,

@@ -158,6 +158,11 @@ void launch_frame_open_v4(const uint8_t* frame, uint64_t avail, uint32_t n_block
 // with skip[b] != 0 are left alone (null: none).  size_hint as for launch_crc32_blocks
 void launch_shuffle_blocks(const uint8_t* src, const uint64_t* off, uint32_t n_ranges, uint32_t elem_bytes,
                            bool inverse, uint8_t* dst, const uint32_t* skip, uint64_t size_hint, hipStream_t stream);
+// the same for ranges of mixed element size in one launch: elem[b] = 2, 4 or 8 is launch_shuffle_blocks' transform of
+// range b with that element size, 0 copies the range as it is (same row rules, same alignment freedom); any other
+// value, like skip[b] != 0, leaves the range alone
+void launch_shuffle_ranges(const uint8_t* src, const uint64_t* off, const uint32_t* elem, uint32_t n_ranges,
+                           bool inverse, uint8_t* dst, const uint32_t* skip, uint64_t size_hint, hipStream_t stream);
 // a ranged read's last step but one: *status = the frame's status, else the first non-zero err[0 .. n_sel); and the
 // one-range work list of launch_range_copy(src, plan, dst, plan + 2, plan + 2, (uint32_t*)(plan + 4), 1, ..):
 // `length` bytes from src + src_at to dst, masked out unless *status == 0.  plan: 5 x uint64
@@ -295,5 +300,27 @@ void launch_frames_open(const uint8_t* frames, const sqz_frames_item* items, con
 void launch_frames_verify(const uint8_t* frames, const sqz_frames_item* items, const uint32_t* base, uint32_t k,
                           const uint32_t* crc, const int32_t* status, const int32_t* err, int32_t* err_out,
                           hipStream_t stream);
+// The flavours that know version 4: elem[f] (k words: 0, 2, 4 or 8) is frame f's element size, 0 an unshuffled frame.
+// encode_scan_v4: a shuffled frame's bound is sqz_frame_bound_shuf's (the record's 8 bytes in front of the padding).
+// plan_v4: in addition blk_elem (total blocks entries) = the element size of every block, for launch_shuffle_ranges.
+// index_v4: frame f is launch_frame_index_v4's where elem[f] != 0 (flags bit 2, the record, which the checksum covers).
+// open_v4: items[f].zero carries the caller's element size for frame f.  A version-4 header is opened by
+//   launch_frame_open_v4 with it (EINVAL when it is 0), a version-1 or -2 header as above (EINVAL when it is not 0),
+//   version 3 is EINVAL.  ent_elem (total blocks + k entries): the element size of every entry, 0 for the switched-off
+//   one of every frame.  The caller made sure that avail covers the record where the element size is not 0.
+void launch_frames_encode_scan_v4(const uint64_t* content_bytes, const uint32_t* elem, uint32_t k, uint32_t block_bits,
+                                  uint32_t flags, uint64_t* in_at, uint64_t* frame_at, uint32_t* base,
+                                  hipStream_t stream);
+void launch_frames_plan_v4(const uint64_t* content_bytes, const uint32_t* elem, const uint64_t* in_at,
+                           const uint32_t* base, uint32_t k, uint32_t block_bits, uint64_t slab_bytes, uint64_t* in_off,
+                           uint64_t* slab_off, uint32_t* blk_elem, hipStream_t stream);
+void launch_frames_index_v4(const uint64_t* out_bytes, const int32_t* err, const uint32_t* crc,
+                            const uint64_t* content_bytes, const uint32_t* elem, const uint64_t* frame_at,
+                            const uint32_t* base, uint32_t k, uint32_t win_bits, uint32_t block_bits, uint32_t flags,
+                            uint8_t* frames, uint64_t* copy_bytes, uint64_t* dense_rel, uint64_t* dense_off,
+                            uint32_t* stored, uint64_t* frame_bytes_out, int32_t* status_out, hipStream_t stream);
+void launch_frames_open_v4(const uint8_t* frames, const sqz_frames_item* items, const uint32_t* base, uint32_t k,
+                           uint64_t out_base, uint64_t* in_off, uint64_t* out_off, uint32_t* skip, uint32_t* stored,
+                           uint32_t* ent_elem, int32_t* status_out, hipStream_t stream);
 
 } // namespace sqzk

@@ -21,6 +21,10 @@ shuffle=2|4|8 / --shuffle N writes version 4: every block is byte-shuffled in fr
 of its N-byte elements, then all second bytes, and so on -- which is what arrays of numbers want (README has the
 figures; noise gains nothing and a few inputs lose a little, so it is opt-in).  The readers pick the version up from
 the header.  Not together with a dictionary; gather, update and append do not take version 4 yet.
+The batch calls (frames_bound, encode_frames, compress_frames) take shuffle= as well: one element size for every frame
+or a sequence with one per frame, 0 for a frame that is not shuffled -- a set of tensors in one launch chain; and
+decode_frames / decompress_frames take versions 1, 2 and 4 in any mix with shuffled=True.  The defaults are the calls
+as they were, which write versions 1 and 2 and refuse a version-4 frame.
 """
 import collections
 import ctypes as C
@@ -668,26 +672,60 @@ def _pinned(array):
     return table
 
 
-def frames_bound(sizes, block_bits: int = 18, store: bool = False):
+def _frames_shuffle(shuffle, k, who):
+    """shuffle= of a batch call: None for the call as it always was (None or 0), else k element sizes out of 0, 2, 4, 8
+    (an int for every frame, or a sequence with one per frame); anything else is ValueError"""
+    if shuffle is None:
+        return None
+    if isinstance(shuffle, bool):
+        raise ValueError(f"{who}: shuffle must be None, 0, 2, 4, 8 or a sequence of these, not {shuffle!r}")
+    if isinstance(shuffle, int):
+        if shuffle not in (0, 2, 4, 8):
+            raise ValueError(f"{who}: shuffle must be 0, 2, 4 or 8, not {shuffle!r}")
+        return None if shuffle == 0 else [shuffle] * k
+    if isinstance(shuffle, (str, bytes, bytearray)):
+        raise ValueError(f"{who}: shuffle must be None, 0, 2, 4, 8 or a sequence of these, not {shuffle!r}")
+    try:
+        elems = list(shuffle)
+    except TypeError:
+        raise ValueError(f"{who}: shuffle must be None, 0, 2, 4, 8 or a sequence of these, not {shuffle!r}") from None
+    if len(elems) != k:
+        raise ValueError(f"{who}: shuffle has {len(elems)} element sizes for {k} frames")
+    for e in elems:
+        if isinstance(e, bool) or not isinstance(e, int) or e not in (0, 2, 4, 8):
+            raise ValueError(f"{who}: every element size must be 0, 2, 4 or 8, not {e!r}")
+    return [int(e) for e in elems]
+
+
+def frames_bound(sizes, block_bits: int = 18, store: bool = False, shuffle=None):
     """Where encode_frames puts the frames of contents of `sizes` bytes: (total, frame_at) -- frame f starts at
     frame_at[f], a multiple of 16, and has its worst-case size (frame_bound) of room; total is the size of the
-    buffer.  Host code: no device is touched."""
+    buffer.  shuffle: as for encode_frames -- a shuffled frame has 8 bytes more in front of its payload.
+    Host code: no device is touched."""
     host = _frames_sizes(sizes, "frames_bound")
     _frames_bits(None, block_bits, "frames_bound")
     k = len(host)
+    elems = _frames_shuffle(shuffle, k, "frames_bound")
     arr = (C.c_uint64 * max(k, 1))(*host)
     at = (C.c_uint64 * (k + 1))()
-    total = int(N.lib().sqz_hip_frames_bound(arr, k, block_bits, _flags(store), at))
+    if elems is not None:
+        el = (C.c_uint32 * max(k, 1))(*elems)
+        total = int(N.lib().sqz_hip_frames_bound_shuf(arr, el, k, block_bits, _flags(store), at))
+    else:
+        total = int(N.lib().sqz_hip_frames_bound(arr, k, block_bits, _flags(store), at))
     if total == 0 and k > 0:
         raise ValueError("frames_bound: the sizes add up to more than a batch holds")
     return total, [int(v) for v in at[:k]]
 
 
 def encode_frames(d_in, sizes, win_bits: int = 15, block_bits: int = 18, store: bool = False, parse: str = "greedy",
-                  d_out=None, scratch=None):
+                  d_out=None, scratch=None, shuffle=None):
     """Many frames in one call: the contents lie back to back in d_in (uint8), sizes[f] bytes each, and frame f is
     written at d_frames[frame_at[f]:] -- byte for byte the frame FrameEncoder writes for that content alone with the
     same arguments (versions 1 and 2).  The launches do not depend on the number of frames.
+    shuffle: None or 0 is the call as it always was.  2, 4 or 8 shuffles every frame with that element size; a sequence
+    of len(sizes) values out of 0, 2, 4, 8 gives every frame its own (0: not shuffled) -- frame f is then byte for byte
+    FrameEncoder(..., shuffle=shuffle[f])'s, version 4 where it is shuffled; one more launch shuffles the whole batch.
     Enqueues and returns (d_frames, frame_at, d_frame_bytes int64[k], d_err int32[total blocks], d_status int32[k]):
     frame_at is frames_bound()'s host list, everything else device tensors to read after a synchronise.  Frame f is
     d_frames[frame_at[f] : frame_at[f] + d_frame_bytes[f]] when d_status[f] is 0; a frame with a failed block has
@@ -698,9 +736,10 @@ def encode_frames(d_in, sizes, win_bits: int = 15, block_bits: int = 18, store: 
     code = parse_code(parse)
     host = _frames_sizes(sizes, "encode_frames")
     _frames_bits(win_bits, block_bits, "encode_frames")
-    L = N.lib()
     k = len(host)
-    total, frame_at = frames_bound(host, block_bits, store)
+    elems = _frames_shuffle(shuffle, k, "encode_frames")
+    L = N.lib()
+    total, frame_at = frames_bound(host, block_bits, store, elems)
     if d_in.dtype != torch.uint8 or d_in.dim() != 1 or d_in.numel() < sum(host):
         raise ValueError("encode_frames: d_in must be a one-dimensional uint8 tensor that holds all the contents")
     device = d_in.device
@@ -713,6 +752,15 @@ def encode_frames(d_in, sizes, win_bits: int = 15, block_bits: int = 18, store: 
     status = torch.zeros(max(k, 1), dtype=torch.int32, device=device)
     err = torch.zeros(max(blocks, 1), dtype=torch.int32, device=device)
     table = _pinned(np.asarray(host, np.uint64)) if k > 0 else None
+    if elems is not None:
+        el = _pinned(np.asarray(elems, np.uint32)) if k > 0 else None
+        if scratch is None:
+            need = int(L.sqz_hip_frames_encode_scratch_bytes_shuf(_ptr(table), _ptr(el), k, block_bits, _flags(store)))
+            scratch = _scratch_for(device, max(need, 16))
+        _raise(L.sqz_hip_frames_encode_shuf(_ptr(d_in), _ptr(table), _ptr(el), k, win_bits, block_bits, _flags(store),
+                                            code, _ptr(d_out), d_out.numel(), _ptr(frame_bytes), _ptr(status), _ptr(err),
+                                            _ptr(scratch), scratch.numel(), _stream()), "sqz_hip_frames_encode_shuf")
+        return d_out, frame_at, frame_bytes[:k], err[:blocks], status[:k]
     if scratch is None:
         need = int(L.sqz_hip_frames_encode_scratch_bytes(_ptr(table), k, block_bits, _flags(store)))
         scratch = _scratch_for(device, max(need, 16))
@@ -740,7 +788,26 @@ def _info_or_nothing(header: bytes):
         return {"n_blocks": 0, "content_bytes": 0}
 
 
-def decode_frames(d_frames, frame_at, infos=None, d_out=None, out_at=None, scratch=None):
+def _records_dev(d_frames, frame_at, infos):
+    """the element sizes of the version-4 frames among `infos`, read from the 8-byte records behind their indexes in
+    one gathered copy (0 for every other frame, and for a record out of reach or with no element size in it: the
+    device refuses such a frame, and alone)"""
+    import torch
+    elems = [0] * len(infos)
+    where = [(f, frame_at[f] + HEADER_BYTES + 8 * int(i["n_blocks"])) for f, i in enumerate(infos)
+             if i.get("version") == 4]
+    where = [(f, a) for f, a in where if a + 8 <= d_frames.numel()]
+    if where:
+        at = torch.tensor([a for _, a in where], dtype=torch.int64, device=d_frames.device)
+        idx = at[:, None] + torch.arange(8, device=d_frames.device)[None, :]
+        raw = d_frames[idx.reshape(-1)].cpu().numpy().tobytes()
+        for j, (f, _) in enumerate(where):
+            e = int.from_bytes(raw[8 * j:8 * j + 4], "little")
+            elems[f] = e if e in (2, 4, 8) else 0
+    return elems
+
+
+def decode_frames(d_frames, frame_at, infos=None, d_out=None, out_at=None, scratch=None, shuffled: bool = False):
     """Many device-resident frames in one call: frame f lies at d_frames[frame_at[f]:] (frame_at: ascending multiples
     of 16; a frame reaches at most to the next one, the last to the end of the tensor), any mix of versions 1 and 2,
     each with its own win_bits and block_bits.  infos: a list of frame_info() dicts of the headers; without it the
@@ -750,7 +817,10 @@ def decode_frames(d_frames, frame_at, infos=None, d_out=None, out_at=None, scrat
     Enqueues and returns (d_out, out_at, d_err int32[total blocks], d_status int32[k]); frame f's blocks are
     d_err[sum(n_blocks[:f]):].  A frame that is refused (a header or index that does not hold; version 3 or 4: EINVAL)
     has its status in d_status[f] and in all its d_err, and nothing of its output is written; a block whose checksum
-    does not hold is EILSEQ in d_err.  Either costs the other frames nothing."""
+    does not hold is EILSEQ in d_err.  Either costs the other frames nothing.
+    shuffled=True takes versions 1, 2 and 4 in any mix (version 3 stays EINVAL): a version-4 frame is decoded by
+    infos[f]["elem_bytes"] (frame_info() of header, index AND record); without infos the records of the version-4
+    frames are read from the device in one more gathered copy.  One more launch shuffles the whole batch back."""
     import numpy as np
     import torch
     frame_at = [int(v) for v in frame_at]
@@ -767,8 +837,14 @@ def decode_frames(d_frames, frame_at, infos=None, d_out=None, out_at=None, scrat
         raise ValueError("decode_frames: frame_at must be ascending and inside d_frames")
     L = N.lib()
     device = d_frames.device
+    elems = [0] * k
     if infos is None:
         infos = [_info_or_nothing(h) for h in _headers_dev(d_frames, frame_at)] if k > 0 else []
+        if shuffled:
+            elems = _records_dev(d_frames, frame_at, infos)
+    elif shuffled:
+        elems = [int(i.get("elem_bytes") or 0) if i.get("version") == 4 else 0 for i in infos]
+        elems = [e if e in (2, 4, 8) else 0 for e in elems]
     sizes = [int(i["content_bytes"]) for i in infos]
     counts = [int(i["n_blocks"]) for i in infos]
     if out_at is None:
@@ -783,12 +859,20 @@ def decode_frames(d_frames, frame_at, infos=None, d_out=None, out_at=None, scrat
     items = np.zeros(max(k, 1), np.dtype([("frame_at", "<u8"), ("avail", "<u8"), ("content_bytes", "<u8"),
                                           ("out_at", "<u8"), ("n_blocks", "<u4"), ("zero", "<u4")]))
     for f in range(k):
-        items[f] = (frame_at[f], ends[f] - frame_at[f], sizes[f], out_at[f], counts[f], 0)
+        items[f] = (frame_at[f], ends[f] - frame_at[f], sizes[f], out_at[f], counts[f], elems[f])
     table = _pinned(items) if k > 0 else None
     blocks = sum(counts)
     err = torch.zeros(max(blocks, 1), dtype=torch.int32, device=device)
     status = torch.zeros(max(k, 1), dtype=torch.int32, device=device)
-    if k > 0:
+    if k > 0 and shuffled:
+        if scratch is None:
+            need = int(L.sqz_hip_frames_decode_scratch_bytes_shuf(_ptr(table), k))
+            if need == 0:
+                raise ValueError("decode_frames: frames or outputs that are not ascending and disjoint")
+            scratch = _scratch_for(device, need)
+        _raise(L.sqz_hip_frames_decode_shuf(_ptr(d_frames), _ptr(table), k, _ptr(d_out), _ptr(err), _ptr(status),
+                                            _ptr(scratch), scratch.numel(), _stream()), "sqz_hip_frames_decode_shuf")
+    elif k > 0:
         if scratch is None:
             need = int(L.sqz_hip_frames_decode_scratch_bytes(_ptr(table), k))
             if need == 0:
@@ -800,19 +884,21 @@ def decode_frames(d_frames, frame_at, infos=None, d_out=None, out_at=None, scrat
 
 
 def compress_frames(datas, win_bits: int = 15, block_bits: int = 18, store: bool = False,
-                    parse: str = "greedy") -> list:
+                    parse: str = "greedy", shuffle=None) -> list:
     """compress_frame() of every item of `datas` (versions 1 and 2) in one device call: one upload, one synchronise,
-    one download.  Raises SqzError naming the first frame that failed."""
+    one download.  Raises SqzError naming the first frame that failed.
+    shuffle: as for encode_frames -- compress_frame(d, ..., shuffle=e) for every item, or for item f with shuffle[f]."""
     import torch
     parse_code(parse)                                        # argument errors before anything is uploaded
     _frames_bits(win_bits, block_bits, "compress_frames")
     datas = [bytes(d) for d in datas]
+    elems = _frames_shuffle(shuffle, len(datas), "compress_frames")
     if not datas:
         return []
     blob = b"".join(datas)
     d_in = torch.frombuffer(bytearray(blob or b"\0"), dtype=torch.uint8)[:len(blob)].to("cuda")
     d_frames, frame_at, frame_bytes, _, status = encode_frames(d_in, [len(d) for d in datas], win_bits, block_bits,
-                                                               store, parse)
+                                                               store, parse, shuffle=elems)
     torch.cuda.synchronize()
     sizes, states = frame_bytes.cpu().tolist(), status.cpu().tolist()
     for f, st in enumerate(states):
@@ -822,11 +908,12 @@ def compress_frames(datas, win_bits: int = 15, block_bits: int = 18, store: bool
     return [host[a:a + n].tobytes() for a, n in zip(frame_at, sizes)]
 
 
-def decompress_frames(frames, return_errors: bool = False):
+def decompress_frames(frames, return_errors: bool = False, shuffled: bool = False):
     """decompress_frame() of every item of `frames` (versions 1 and 2, any mix of parameters) in one device call: one
     upload, one synchronise, one download.  Raises SqzError naming the first frame that did not hold -- its status, or
     its first failed block -- unless return_errors is set: then (contents, errors) with errors[f] = (status,
-    block_errors); good frames and good blocks are delivered, a refused frame is b""."""
+    block_errors); good frames and good blocks are delivered, a refused frame is b"".
+    shuffled=True takes version 4 as well (decode_frames); the element sizes are read from the frames' records."""
     import numpy as np
     import torch
     frames = [bytes(f) for f in frames]
@@ -842,7 +929,12 @@ def decompress_frames(frames, return_errors: bool = False):
     for a, f in zip(frame_at, frames):
         image[a:a + len(f)] = np.frombuffer(f, np.uint8)
     d_frames = torch.from_numpy(image)[:at].to("cuda")
-    d_out, out_at, err, status = decode_frames(d_frames, frame_at, infos)
+    if shuffled:                                             # the records are at hand: no copy back from the device
+        for j, (f, info) in enumerate(zip(frames, infos)):
+            at = HEADER_BYTES + 8 * info["n_blocks"]
+            if info.get("version") == 4 and len(f) >= at + 8:
+                infos[j] = dict(info, elem_bytes=int.from_bytes(f[at:at + 4], "little"))
+    d_out, out_at, err, status = decode_frames(d_frames, frame_at, infos, shuffled=shuffled)
     torch.cuda.synchronize()
     host, errs, states = d_out.cpu().numpy(), err.cpu().tolist(), status.cpu().tolist()
     contents, errors, b0 = [], [], 0
